@@ -25,6 +25,15 @@ plot/summarize_data.py:24-48): an event pair per iteration on the stream the
 collective is issued on (K iterations back to back between a barrier +
 device synchronize on both sides), the max over ranks per iteration, the
 first 20 % dropped, the median.  One JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+`--steps` calls, print the line (at N > 1 the transport trials stay: they pick
+the configuration the headline is).  `--full` adds everything measured beside
+it: the output's digest check and the roofline run at N = 1, the side kernels,
+the CPU baseline, and at N > 1 the step profile, C1 / C4 / C5, the probes and
+RCCL's own allreduce.  `--dump-outputs DIR` writes what the timed call left in
+its receive buffer after the last timed step as DIR/<name>.npy (float32; a
+fixed seeded sample when the buffer is larger than DUMP_MAX_ELEMS).
 """
 from __future__ import annotations
 
@@ -332,6 +341,34 @@ def _r(x, n=4):
     return None if x is None else round(x, n)
 
 
+# ---- --dump-outputs ----------------------------------------------------------------
+
+DUMP_MAX_ELEMS = 4 << 20       # elements written per array (16 MiB of float32)
+DUMP_SEED = 20240229
+
+
+def dump_indices(n: int):
+    """the elements of an n-element output that --dump-outputs writes: all of
+    them up to DUMP_MAX_ELEMS, else a fixed sample (numpy PCG64 seeded with
+    DUMP_SEED, sorted) -- the same for every run and build at the same n"""
+    import numpy as np
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    idx = np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64)
+    idx.sort()
+    return idx
+
+
+def dump_output(torch, out_dir: str, name: str, buf, n: int):
+    """out_dir/name.npy: the first n elements of the device buffer `buf` (or
+    their dump_indices sample) as float32"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = dump_indices(n)
+    t = buf[:n] if idx is None else buf[:n][torch.from_numpy(idx).to(buf.device)]
+    np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 # ---- CPU baseline (rank 0, N = 1) --------------------------------------------------
 
 def _ref_bench(np_: int, args, timeout: float):
@@ -556,7 +593,7 @@ def _side_small_windows(torch, pico_amd, dev, stream):
     return out
 
 
-def bench_n1(steps: int, warmup: int, want_cpu: bool, cpu_budget: float):
+def bench_n1(steps: int, warmup: int, want_cpu: bool, cpu_budget: float, full: bool = False, dump_dir=None):
     import pico_amd
     import torch
     dev = torch.device("cuda:0")
@@ -573,23 +610,10 @@ def bench_n1(steps: int, warmup: int, want_cpu: bool, cpu_budget: float):
     call = lambda: pico_amd.allreduce("bine_bdw_remap", sbuf, rbuf, n, "float", "sum", comm,  # noqa: E731
                                       stream=stream)
     st = timed(torch, stream, call, steps, warmup, syncs=(comm.synchronize,))
-    # the kernel's average launch duration for the roofline: the same K calls
-    # back to back with one event pair around them (per-iteration events add a
-    # dispatch bubble each; this is what a kernel-trace average reports)
-    st_k = timed(torch, stream, call, steps, 2, syncs=(comm.synchronize,), per_iter=False)
-    key = gkey("C3", "allreduce", "bine_bdw_remap", "float", n, 1)
-    ok, dig = check_digest(pico_amd, rbuf, n, "float", key, 0)
-    ok_in, _ = check_digest(pico_amd, sbuf, n, "float", key, 0)   # input untouched (P = 1: output == input)
-    comm.destroy()
-    del sbuf, rbuf
-    torch.cuda.empty_cache()
+    if dump_dir:
+        dump_output(torch, dump_dir, "allreduce_rbuf", rbuf, n)
     ms = st["median_ms"]
     algbw = S / (ms * 1e-3) / 1e9
-    hbm = 2 * S / (st_k["region_ms"] * 1e-3) / 1e9
-    side = {"k_reduce_C2": _side_reduce(torch, pico_amd, dev, stream, steps, warmup),
-            "k_reduce_tree_C3_flat_rs_chunk": _side_tree(torch, pico_amd, dev, stream, steps, warmup)}
-    if os.environ.get("BENCH_NO_SMALL_WINDOWS") != "1":   # PMC passes: one k_reduce shape only
-        side["k_reduce_small_windows"] = _side_small_windows(torch, pico_amd, dev, stream)
     out = {
         "metric": METRIC, "value": round(algbw, 2), "unit": "GB/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
         "ms_per_step": round(ms, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -600,10 +624,32 @@ def bench_n1(steps: int, warmup: int, want_cpu: bool, cpu_budget: float):
                    "value_definition": "per-rank algbw = S / t, t = median after dropping the first 20 % of "
                                        "per-iteration event times (pico_core.c:133-140, summarize_data.py:24-48)",
                    "stats_ms": {k: _r(v, 5) for k, v in st.items()},
+                   "rccl": pico_amd.rccl_version(), "host": host_info()},
+        "wall_s": round(st["wall_s"], 4),
+    }
+    if not full:
+        comm.destroy()
+        return out
+    # the kernel's average launch duration for the roofline: the same K calls
+    # back to back with one event pair around them (per-iteration events add a
+    # dispatch bubble each; this is what a kernel-trace average reports)
+    st_k = timed(torch, stream, call, steps, 2, syncs=(comm.synchronize,), per_iter=False)
+    key = gkey("C3", "allreduce", "bine_bdw_remap", "float", n, 1)
+    ok, dig = check_digest(pico_amd, rbuf, n, "float", key, 0)
+    ok_in, _ = check_digest(pico_amd, sbuf, n, "float", key, 0)   # input untouched (P = 1: output == input)
+    comm.destroy()
+    del sbuf, rbuf
+    torch.cuda.empty_cache()
+    hbm = 2 * S / (st_k["region_ms"] * 1e-3) / 1e9
+    side = {"k_reduce_C2": _side_reduce(torch, pico_amd, dev, stream, steps, warmup),
+            "k_reduce_tree_C3_flat_rs_chunk": _side_tree(torch, pico_amd, dev, stream, steps, warmup)}
+    if os.environ.get("BENCH_NO_SMALL_WINDOWS") != "1":   # PMC passes: one k_reduce shape only
+        side["k_reduce_small_windows"] = _side_small_windows(torch, pico_amd, dev, stream)
+    out["config"].update({
                    "parity": {"ok": bool(ok) and bool(ok_in), "check": "bine_checksum(rbuf) == oracle digest "
                               f"{key} (tests/golden/bench_digests.json), input untouched", "digest": str(dig)},
-                   "rccl": pico_amd.rccl_version(), "host": host_info(),
-                   "side_kernels": side},
+                   "side_kernels": side})
+    out.update({
         "roofline": {"bound": "hbm", "achieved": round(hbm, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(hbm / HBM_PEAK_GBS, 4), "traffic": _pmc_traffic("k_copy"),
                      "kernel": "bine::k_copy (the P = 1 allreduce is one launch)",
@@ -613,9 +659,7 @@ def bench_n1(steps: int, warmup: int, want_cpu: bool, cpu_budget: float):
                              "(one k_copy launch each) back to back between one HIP event pair on the launch "
                              "stream (agrees with the kernel-trace average, profiles/r4_bench_kernel_stats.csv); "
                              "traffic = PMC FETCH_SIZE x 2 (gfx950) + WRITE_SIZE per launch "
-                             "(profiles/latest_pmc.json)"},
-        "wall_s": round(st["wall_s"], 4),
-    }
+                             "(profiles/latest_pmc.json)"}})
     if want_cpu:
         out["cpu_baseline"] = cpu_baseline(dig, cpu_budget)
     return out
@@ -1108,7 +1152,7 @@ def arm_deadline(budget_s, payload, what):
 
 
 def bench_allreduce(steps: int, warmup: int, nelem: int, algo: str, relay: str, extras: bool = True,
-                    chunk_mib: int = 0, graph_trial: bool = True):
+                    chunk_mib: int = 0, graph_trial: bool = True, full: bool = False, dump_dir=None):
     import pico_amd
     import torch
     import torch.distributed as dist
@@ -1333,6 +1377,22 @@ def bench_allreduce(steps: int, warmup: int, nelem: int, algo: str, relay: str, 
     watchdog.cancel()
     ms = st["median_ms"]
     out = headline(best, st, ok_head, dig, ok_trees_tol)
+    if out is not None:
+        out["config"]["provisional_literal_rccl"] = {"ms": round(st0["median_ms"], 4),
+                                                     "algbw_per_rank_GBs": round(S / (st0["median_ms"] * 1e-3) / 1e9, 2),
+                                                     "parity_ok": ok0}
+    if dump_dir:
+        # the headline configuration's output: every transport but multi-tree
+        # mode leaves the same bits, so one more call of it (not timed) stands
+        # for its last timed step whichever configuration was timed last
+        run()
+        torch.cuda.synchronize()
+        comm.synchronize()
+        dump_output(torch, dump_dir, f"allreduce_rbuf_rank{rank}", rbuf, nelem)
+    if not full:
+        comm.destroy()
+        dist.destroy_process_group()
+        return out
     # the side measurements below run under a deadline: if one of them hangs
     # (an RCCL or transport fault in a secondary configuration), every rank
     # stops at the same budget and rank 0 still prints the headline line with
@@ -1372,10 +1432,7 @@ def bench_allreduce(steps: int, warmup: int, nelem: int, algo: str, relay: str, 
         out["config"].update({"step_profile_rank0": steps_prof, "other_baseline_configs": extra,
                               "rccl_p2p_probe": probe, "rccl_allreduce_baseline": vendor,
                               "direct_transport_probe": dprobe,
-                              "transport_trials_ms": {tname(c): round(v, 4) for c, v in trials.items()},
-                              "provisional_literal_rccl": {"ms": round(st0["median_ms"], 4),
-                                                           "algbw_per_rank_GBs": round(S / (st0["median_ms"] * 1e-3) / 1e9, 2),
-                                                           "parity_ok": ok0}})
+                              "transport_trials_ms": {tname(c): round(v, 4) for c, v in trials.items()}})
         out["config"]["parity"]["trials"] = {tname(c): v for c, v in verdicts.items()}
     if rank == 0 and dprobe.get("push_GBs_median"):
         # the node model again with the measured constants in place of the
@@ -1526,14 +1583,20 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="N > 1: skip the C1/C4/C5 side measurements")
     ap.add_argument("--no-graph-trial", action="store_true", help="N > 1: do not trial HIP-graph replay")
     ap.add_argument("--cpu-budget", type=float, default=5.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything measured beside the headline: digest check, roofline run, side kernels "
+                         "and CPU baseline at N = 1; step profile, C1/C4/C5, probes and RCCL's allreduce at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the receive buffer of the last timed step to DIR/<name>.npy (float32; a fixed "
+                         "seeded sample of a large buffer)")
     args = ap.parse_args()
     if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         res = bench_allreduce(args.steps, args.warmup, args.elems, args.algo, args.relay, not args.no_extras,
-                              args.chunk_mib, not args.no_graph_trial)
+                              args.chunk_mib, not args.no_graph_trial, args.full, args.dump_outputs)
         if res is not None:
             print(json.dumps(res), flush=True)
         return
-    res = bench_n1(args.steps, args.warmup, not args.no_cpu_baseline, args.cpu_budget)
+    res = bench_n1(args.steps, args.warmup, not args.no_cpu_baseline, args.cpu_budget, args.full, args.dump_outputs)
     print(json.dumps(res), flush=True)
 
 

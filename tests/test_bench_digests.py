@@ -7,7 +7,7 @@ recomputed here with the oracle; C3 at P = 1 is the digest of pico_core's
 seed-1234 input (the reference's P = 1 allreduce copies it).  The full-size
 C3 entries at P = 1, 2, 4, 8 were also checked against the REAL reference's
 output digests (oracle/_ref/ref_bench; profiles/r2_c3_digests_vs_reference.txt),
-and bench.py re-checks them in every N = 1 run through the cpu_baseline leg.
+and bench.py --full re-checks them in every N = 1 run through the cpu_baseline leg.
 """
 import json
 import os

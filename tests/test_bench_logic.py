@@ -67,3 +67,22 @@ def test_step_profile_counts_trees_inside_exchanges_as_no_local_time():
     assert p["local_busy_ms"] == 0.2 and p["ops"] == 3
     assert p["local"][0]["inside_exchange"] and p["local"][0]["hbm_GBs"] is None
     assert "inside_exchange" not in p["local"][1] and p["local"][1]["hbm_GBs"] > 0
+
+
+def test_dump_outputs_sample_is_fixed_and_float32(tmp_path):
+    """--dump-outputs: a buffer up to DUMP_MAX_ELEMS is written whole, a larger
+    one as the same sorted in-range sample every time, both as float32"""
+    import numpy as np
+    import torch
+    assert bench.dump_indices(bench.DUMP_MAX_ELEMS) is None
+    n = bench.DUMP_MAX_ELEMS + 12345
+    idx = bench.dump_indices(n)
+    assert idx.shape == (bench.DUMP_MAX_ELEMS,) and idx[0] >= 0 and idx[-1] < n and np.all(np.diff(idx) >= 0)
+    assert np.array_equal(idx, bench.dump_indices(n))
+    assert 4 * bench.DUMP_MAX_ELEMS <= 64 << 20
+    buf = torch.arange(n + 7, dtype=torch.float64)            # a buffer longer than its n used elements
+    bench.dump_output(torch, str(tmp_path / "d"), "big", buf, n)
+    bench.dump_output(torch, str(tmp_path / "d"), "small", buf, 1000)
+    big, small = np.load(tmp_path / "d" / "big.npy"), np.load(tmp_path / "d" / "small.npy")
+    assert big.dtype == np.float32 and np.array_equal(big, idx.astype(np.float32))
+    assert small.dtype == np.float32 and np.array_equal(small, np.arange(1000, dtype=np.float32))

@@ -1,5 +1,5 @@
 """The driver's N > 1 bench command, end to end, on the test box's one GPU:
-`torch.distributed.run --nproc-per-node 2 bench.py --gpus 2` with two
+`torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 --full` with two
 processes sharing the device (distinct NCCL_HOSTIDs, RCCL's socket transport;
 BINE_FAKE_HOSTS=1).  The speeds say nothing about xGMI; what is checked is
 the path the driver's multi-GPU run takes: the provisional literal-schedule
@@ -31,7 +31,7 @@ def test_bench_two_ranks_one_gpu():
     env = dict(os.environ, BINE_FAKE_HOSTS="1", PYTHONPATH=ROOT)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "5", "--warmup", "1"]
+           "--gpus", "2", "--steps", "5", "--warmup", "1", "--full"]
     r = _sub.run_kw(cmd, env=env, capture_output=True, text=True, timeout=380, cwd=ROOT, ranks=2)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

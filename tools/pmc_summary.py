@@ -12,7 +12,7 @@ roofline kernel is the largest-grid shape.  HBM bytes per launch follow
 MI355X_MICROARCH.md "HBM": FETCH_SIZE and WRITE_SIZE are in KiB; on gfx950
 FETCH_SIZE reads exactly half the bytes of a wide coalesced streaming read, so
 reads = 2 * FETCH_SIZE; writes = WRITE_SIZE.
-usage: python tools/pmc_summary.py TAG
+usage: python tools/pmc_summary.py TAG [DIR]   (DIR: where the passes were written, if elsewhere)
 """
 import csv
 import glob
@@ -24,6 +24,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "gpurun_out")
+if len(sys.argv) > 2:
+    OUT = os.path.abspath(sys.argv[2])
 
 
 def short(name):
