@@ -26,7 +26,29 @@
 extern "C" {
 #endif
 
-/* element types; same numbering as the test oracle (oracle/bine_oracle.h) */
+/* element types.  Codes 0..16 are MPICH 3.3.2's reduction types, with the same
+ * numbering as the test oracle (oracle/bine_oracle.h); BINE_NUM_DTYPES counts
+ * those alone.  The 16-bit floating types live in a separate extension range
+ * [BINE_EXT_DTYPE_FIRST, BINE_EXT_DTYPE_END): MPICH has no datatype for them,
+ * so the oracle's numbering cannot grow.  Codes 17..31 and 34 and up are
+ * invalid.
+ *
+ * BINE_FLOAT16 (IEEE binary16) and BINE_BFLOAT16 (the upper half of a
+ * binary32), 2 bytes each, reduce under SUM / PROD / MAX / MIN only
+ * (BINE_ERR_ARG with every other op); the data-movement collectives carry
+ * them as any 2-byte type.  Each pairwise reduction inout (op) in is the IEEE
+ * correctly rounded result IN THE 16-BIT FORMAT: round to nearest even,
+ * subnormals kept on input and output, no FMA.  (Computing the sum or product
+ * in binary32 and rounding once gives exactly that: 24 >= 2 * 11 + 2 and
+ * 24 >= 2 * 8 + 2, so the definition does not depend on how it is computed.)
+ * MAX / MIN follow the rule below -- inout > in ? inout : in (resp. <) -- and
+ * copy the selected operand's bits unchanged.  A SUM / PROD whose IEEE result
+ * is NaN yields a NaN of unspecified payload.  Every level of a reduction
+ * tree (bine_reduce_tree, the flat reduce-scatter) rounds to the 16-bit type,
+ * as the literal schedule does by storing each intermediate in memory: the
+ * flat forms stay bit-identical to it.  Not provided for these types:
+ * bine_fill_pico (BINE_ERR_UNSUPPORTED), bine_vendor_allreduce
+ * (BINE_ERR_ARG), the libbine.h drop-in. */
 typedef enum {
   BINE_INT8 = 0, BINE_UINT8 = 1, BINE_INT16 = 2, BINE_UINT16 = 3,
   BINE_INT32 = 4, BINE_UINT32 = 5, BINE_INT64 = 6, BINE_UINT64 = 7,
@@ -39,7 +61,11 @@ typedef enum {
   /* C99 complex types {re; im} (MPI_C_FLOAT_COMPLEX, MPI_C_DOUBLE_COMPLEX),
    * SUM / PROD only, as MPICH */
   BINE_C_FLOAT_COMPLEX = 15, BINE_C_DOUBLE_COMPLEX = 16,
-  BINE_NUM_DTYPES = 17
+  BINE_NUM_DTYPES = 17,
+  /* extension range: 16-bit floating types (see above) */
+  BINE_EXT_DTYPE_FIRST = 32,
+  BINE_FLOAT16 = 32, BINE_BFLOAT16 = 33,
+  BINE_EXT_DTYPE_END = 34
 } bine_dtype_t;
 
 /* reduction operators, MPI_Reduce_local semantics of MPICH 3.3.2:
@@ -147,7 +173,8 @@ size_t bine_dtype_size(int dtype);
 /* 1 if MPICH's MPI_Reduce_local accepts (dtype, op): no bitwise op on float /
  * double, MAXLOC / MINLOC exactly on the pair types, SUM / PROD only on the
  * complex types; 0 otherwise (the collectives then return BINE_ERR_ARG, the
- * libbine.h shim MPI_ERR_OP) */
+ * libbine.h shim MPI_ERR_OP).  BINE_FLOAT16 / BINE_BFLOAT16: 1 for SUM, PROD,
+ * MAX and MIN, 0 for every other op */
 int bine_op_valid(int dtype, int op);
 /* -1 if unknown; `collective` = "allreduce" | "reduce_scatter" | "reduce" */
 int bine_algo_from_name(const char *collective, const char *name);
@@ -175,6 +202,12 @@ int bine_reduce_batch(int n, const void *const *a, const void *const *b, void *c
  * operands.  `out` may alias any leaf element for element. */
 int bine_reduce_tree(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
                      void *stream);
+/* The same tree with the operand order of some levels reversed: bit l of
+ * `swap` set = level l (w = 1 << l) computes v[i] = v[i + w] (op) v[i], v[i + w]
+ * the inout side (the flat form of reduce_scatter_bine_block_by_block's last
+ * step).  swap = 0 is bine_reduce_tree. */
+int bine_reduce_tree_swap(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
+                          unsigned swap, void *stream);
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 /* copy_buffer on the device (libbine_utils.h:176-190; the sbuf -> rbuf copy of
  * e.g. allreduce_bine_bdw_remap, libbine_allreduce.c:849-852): dst[0:bytes) =

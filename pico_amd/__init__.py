@@ -5,9 +5,14 @@ reduction kernels, RCCL point-to-point over xGMI.
 The native library lives in pico_amd/lib/ (built in-tree by
 ``__graft_entry__.build()``); this package is a thin ctypes mirror of its C ABI
 (include/bine_amd.h) with the reference's function names.
+
+Element types: ``DTYPES`` are MPICH's 17 reduction types (the reference's);
+``EXT_DTYPES`` adds "float16" and "bfloat16" (torch.float16 / torch.bfloat16),
+reduced under sum / prod / max / min with every pairwise result correctly
+rounded to the 16-bit format.
 """
-from ._lib import ALGOS, DTYPES, OPS, BineError, lib  # noqa: F401
+from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403
 from .api import __all__ as _api_all
 
-__all__ = ["ALGOS", "DTYPES", "OPS", "lib"] + _api_all
+__all__ = ["ALGOS", "DTYPES", "EXT_DTYPES", "OPS", "lib"] + _api_all

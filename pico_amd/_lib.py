@@ -20,10 +20,15 @@ DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "uint16": 3, "int32": 4, "uint32": 
           "float_int": 10, "double_int": 11, "long_int": 12, "2int": 13, "short_int": 14,
           # C99 complex, SUM / PROD only
           "c_float_complex": 15, "c_double_complex": 16}
+# the extension range (BINE_EXT_DTYPE_FIRST..END): the 16-bit floating types,
+# SUM / PROD / MAX / MIN only.  Kept out of DTYPES, which stays MPICH's 17 types
+# (the oracle's numbering)
+EXT_DTYPES = {"float16": 32, "bfloat16": 33}
 DTYPE_SIZE = {"int8": 1, "uint8": 1, "int16": 2, "uint16": 2, "int32": 4, "uint32": 4,
               "int64": 8, "uint64": 8, "float": 4, "double": 8,
               "float_int": 8, "double_int": 16, "long_int": 16, "2int": 8, "short_int": 8,
-              "c_float_complex": 8, "c_double_complex": 16}
+              "c_float_complex": 8, "c_double_complex": 16,
+              "float16": 2, "bfloat16": 2}
 OPS = {"sum": 0, "prod": 1, "max": 2, "min": 3, "land": 4, "band": 5, "lor": 6, "bor": 7, "lxor": 8, "bxor": 9,
        "maxloc": 10, "minloc": 11}
 STATUS = {0: "SUCCESS", 1: "ERR_ARG", 2: "ERR_SIZE", 3: "ERR_NO_MEM", 4: "ERR_HIP", 5: "ERR_RCCL",
@@ -143,6 +148,7 @@ def lib():
         "bine_allgather": ([vp, i, vp, vp, sz, i, vp], i),
         "bine_reduce_batch": ([i, vp, vp, vp, vp, i, i, vp], i),
         "bine_reduce_tree": ([i, vp, vp, ctypes.c_size_t, i, i, vp], i),
+        "bine_reduce_tree_swap": ([i, vp, vp, ctypes.c_size_t, i, i, ctypes.c_uint, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

@@ -4,7 +4,10 @@ Every function named after a libbine entry point (reference include/libbine.h:
 30-78) takes the same arguments in the same order --
 ``allreduce_bine_bdw_remap(sbuf, rbuf, count, dtype, op, comm)`` -- where the
 buffers are device tensors (torch, ROCm) or raw device addresses, ``dtype`` is a
-libbine element-type name ("float", "double", "int32", ...) or a torch dtype,
+libbine element-type name ("float", "double", "int32", ...), one of the 16-bit
+floating types "float16" | "bfloat16" (``EXT_DTYPES``: "sum" / "prod" / "max" /
+"min" only, every pairwise reduction correctly rounded to the 16-bit format) or
+a torch dtype (torch.float16 / torch.bfloat16 included),
 ``op`` is "sum" | "prod" | "max" | "min" | "land" | "lor" | "lxor" | "band" | "bor" | "bxor" |
 "maxloc" | "minloc" (MPICH semantics; bitwise ops on integer types only, the loc ops on
 the pair types "float_int" | "double_int" | "long_int" | "2int" | "short_int" only; the
@@ -20,7 +23,7 @@ import ctypes
 from typing import Optional, Sequence
 
 from . import _lib
-from ._lib import ALGOS, DTYPES, OPS, BineError, check, lib
+from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, check, lib
 
 IN_PLACE = "IN_PLACE"   # libbine's MPI_IN_PLACE
 
@@ -33,7 +36,7 @@ def _torch_dtypes():
         import torch
         _TORCH_DT = {torch.float32: "float", torch.float64: "double", torch.int8: "int8",
                      torch.uint8: "uint8", torch.int16: "int16", torch.int32: "int32",
-                     torch.int64: "int64"}
+                     torch.int64: "int64", torch.float16: "float16", torch.bfloat16: "bfloat16"}
     return _TORCH_DT
 
 
@@ -45,7 +48,7 @@ def _dtype(dtype, *bufs) -> int:
                 break
     if not isinstance(dtype, str):
         dtype = _torch_dtypes()[dtype]
-    return DTYPES[dtype]
+    return DTYPES[dtype] if dtype in DTYPES else EXT_DTYPES[dtype]
 
 
 def _ptr(buf):
@@ -523,9 +526,14 @@ def reduce_batch(ins, inouts, counts, dtype, op: str = "sum", stream=None) -> in
     return lib().bine_reduce_batch(n, _ptrs(ins), b, b, c, _dtype(dtype, inouts[0]), OPS[op], _stream(stream, None))
 
 
-def reduce_tree(leaves, out, count: int, dtype, op: str = "sum", stream=None) -> int:
+def reduce_tree(leaves, out, count: int, dtype, op: str = "sum", stream=None, swap: int = 0) -> int:
     """out[:count] = the reduction tree over the leaf buffers (tree order,
-    len 2/4/8/16) in one launch (bine_reduce_tree).  Returns the status."""
+    len 2/4/8/16) in one launch (bine_reduce_tree; bit l of `swap`: level l
+    takes its right operand as the inout side, bine_reduce_tree_swap).
+    Returns the status."""
+    if swap:
+        return lib().bine_reduce_tree_swap(len(leaves), _ptrs(leaves), _ptr(out), count, _dtype(dtype, out),
+                                           OPS[op], swap, _stream(stream, None))
     return lib().bine_reduce_tree(len(leaves), _ptrs(leaves), _ptr(out), count, _dtype(dtype, out), OPS[op],
                                   _stream(stream, None))
 

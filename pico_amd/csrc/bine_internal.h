@@ -144,6 +144,13 @@ int launch_reduce_batch_logic(int n, const void *const *a, const void *const *b,
                               const size_t *count, int dtype, int op, void *stream);
 int launch_reduce_tree_logic(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
                              void *stream, unsigned swap);
+// the 16-bit floating types' instantiations (kernels.hip compiled with
+// BINE_OPSET=2); the entry points above forward BINE_FLOAT16 / BINE_BFLOAT16 here
+int launch_reduce_h16(const void *a, const void *b, void *out, size_t count, int dtype, int op, void *stream);
+int launch_reduce_batch_h16(int n, const void *const *a, const void *const *b, void *const *out,
+                            const size_t *count, int dtype, int op, void *stream);
+int launch_reduce_tree_h16(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
+                           void *stream, unsigned swap);
 // copy_buffer on the device (k_copy); hipMemcpyAsync when src / dst are not
 // co-aligned mod 16 B
 int launch_copy(void *dst, const void *src, size_t bytes, void *stream);

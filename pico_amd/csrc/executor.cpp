@@ -1684,6 +1684,9 @@ static int hw_queues() {
   return v;
 }
 
+// the extension range of element types (bine_amd.h): float16 / bfloat16
+static bool ext_dtype(int dtype) { return dtype >= BINE_EXT_DTYPE_FIRST && dtype < BINE_EXT_DTYPE_END; }
+
 // chunk_bytes == kCommChunk: the communicator's setting (bine_comm_set_chunk)
 constexpr size_t kCommChunk = ~(size_t)0;
 // op of the data-movement collectives (allgather family): no reduction runs
@@ -1695,7 +1698,7 @@ constexpr int kOpNone = -1;
 static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbuf, int dtype, int op,
                           size_t chunk_bytes, void *stream, Staging *stg = nullptr) {
   if (!c) return BINE_ERR_ARG;
-  if (dtype < 0 || dtype >= BINE_NUM_DTYPES) return BINE_ERR_UNSUPPORTED;
+  if (dtype < 0 || (dtype >= BINE_NUM_DTYPES && !ext_dtype(dtype))) return BINE_ERR_UNSUPPORTED;
   if (op != kOpNone) {
     if (op < 0 || op >= BINE_NUM_OPS) return BINE_ERR_UNSUPPORTED;
     // (op, type) pairs MPICH's MPI_Reduce_local rejects (MPI_ERR_OP): refused
@@ -1824,6 +1827,8 @@ const char *bine_status_string(int s) {
 const char *bine_last_error(void) { return g_err.c_str(); }
 
 int bine_op_valid(int dtype, int op) {
+  // the 16-bit floating types: the four arithmetic ops
+  if (ext_dtype(dtype)) return op >= BINE_SUM && op <= BINE_MIN;
   if (dtype < 0 || dtype >= BINE_NUM_DTYPES || op < 0 || op >= BINE_NUM_OPS) return 0;
   const bool pair = dtype >= BINE_FLOAT_INT && dtype <= BINE_SHORT_INT, loc = op == BINE_MAXLOC || op == BINE_MINLOC;
   if (pair != loc) return 0;  // pair types under MAXLOC / MINLOC only, and those ops on pairs only
@@ -1836,7 +1841,7 @@ int bine_op_valid(int dtype, int op) {
 size_t bine_dtype_size(int dt) {
   switch (dt) {
     case BINE_INT8: case BINE_UINT8: return 1;
-    case BINE_INT16: case BINE_UINT16: return 2;
+    case BINE_INT16: case BINE_UINT16: case BINE_FLOAT16: case BINE_BFLOAT16: return 2;
     case BINE_INT32: case BINE_UINT32: case BINE_FLOAT: return 4;
     case BINE_INT64: case BINE_UINT64: case BINE_DOUBLE: return 8;
     case BINE_FLOAT_INT: case BINE_2INT: case BINE_SHORT_INT: return 8;
@@ -1928,6 +1933,12 @@ int bine_reduce_tree(int nleaves, const void *const *leaves, void *out, size_t c
                      void *stream) {
   if (!leaves || (!out && count)) return BINE_ERR_ARG;
   return launch_reduce_tree(nleaves, leaves, out, count, dtype, op, stream);
+}
+
+int bine_reduce_tree_swap(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
+                          unsigned swap, void *stream) {
+  if (!leaves || (!out && count)) return BINE_ERR_ARG;
+  return launch_reduce_tree(nleaves, leaves, out, count, dtype, op, stream, swap);
 }
 
 int bine_copy(void *dst, const void *src, size_t bytes, void *stream) {

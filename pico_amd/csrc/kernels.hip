@@ -34,18 +34,22 @@
 
 #include "bine_internal.h"
 
-// This file is compiled twice (Makefile): BINE_OPSET 0 -> kernels.o, the
+// This file is compiled three times (Makefile): BINE_OPSET 0 -> kernels.o, the
 // arithmetic ops SUM / PROD / MAX / MIN and every other kernel; BINE_OPSET 1
 // -> kernels_logic.o, the reduction kernels' instantiations for the logical
 // and bitwise ops only (launch_*_logic, reached from the opset-0 entry
-// points).  Two translation units compile in parallel.
+// points); BINE_OPSET 2 -> kernels_h16.o, the reduction kernels'
+// instantiations for the 16-bit floating types (launch_*_h16, reached the
+// same way).  Three translation units compile in parallel.
 #ifndef BINE_OPSET
 #define BINE_OPSET 0
 #endif
 #if BINE_OPSET == 0
 #define BINE_FN(name) name
-#else
+#elif BINE_OPSET == 1
 #define BINE_FN(name) name##_logic
+#else
+#define BINE_FN(name) name##_h16
 #endif
 
 namespace bine {
@@ -101,10 +105,29 @@ struct is_cplx : std::false_type {};
 template <typename V>
 struct is_cplx<Cplx<V>> : std::true_type {};
 
+// The 16-bit floating types of the extension range (BINE_FLOAT16 /
+// BINE_BFLOAT16, bine_amd.h): SUM / PROD / MAX / MIN only.  A sum or product
+// is the IEEE result rounded once to the 16-bit format (nearest even,
+// subnormals kept): binary16 by the native f16 instructions; bfloat16 widened
+// to binary32 (a shift), one fp32 operation -- exact or far more precise than
+// needed: 24 >= 2 * 8 + 2 bits, so the single rounding that follows gives the
+// correctly rounded bfloat16 result -- and the hardware's round-to-nearest-
+// even conversion back.  Every call rounds: the levels of a reduction tree
+// never keep an fp32 intermediate, so the tree kernels give the bits of the
+// literal schedule, which stores every intermediate as a 16-bit value.
+// MAX / MIN compare and select (never v_pk_max / v_pk_min, whose NaN and
+// signed-zero results differ from `io > in ? io : in`).
+using F16 = _Float16;
+using BF16 = __bf16;
+static_assert(sizeof(F16) == 2 && sizeof(BF16) == 2, "16-bit floating types");
+
 // MPICH's MPIR_OP_TYPE_REDUCE_CASE: a = inout, b = in, a = OP(a, b)
 template <typename T, int OP>
 __device__ __forceinline__ T apply(T io, T in) {
-  if constexpr (is_cplx<T>::value) {
+  if constexpr (std::is_same_v<T, BF16> && (OP == BINE_SUM || OP == BINE_PROD)) {
+    const float x = (float)io, y = (float)in;
+    return (BF16)(OP == BINE_SUM ? x + y : x * y);
+  } else if constexpr (is_cplx<T>::value) {
     // MPICH's MPIR_LSUM / MPIR_LPROD on float/double _Complex: component-wise
     // sum; for finite operands the product is (a.re b.re - a.im b.im) +
     // (a.re b.im + a.im b.re) i (a = inout; no FMA: -ffp-contract=off)
@@ -171,7 +194,7 @@ constexpr bool kCplxT = is_cplx<T>::value;
 
 // BINE_OP_SWITCH(T, CALL): `return CALL(OP)` for the op in variable `op`,
 // only for the (T, OP) pairs instantiated; hipErrorInvalidValue otherwise
-#if BINE_OPSET == 0
+#if BINE_OPSET != 1
 #define BINE_OP_SWITCH(T, CALL)                                      \
   switch (op) {                                                      \
     case BINE_SUM: return CALL(BINE_SUM);                            \
@@ -204,10 +227,14 @@ constexpr bool kCplxT = is_cplx<T>::value;
 [[maybe_unused]] static bool ext_op(int dtype, int op) {
   return (op >= BINE_LAND && op < BINE_NUM_OPS) || (dtype >= BINE_FLOAT_INT && dtype < BINE_NUM_DTYPES);
 }
+// the types the opset-2 compilation holds (every op: the ones not defined on
+// them are refused there, by canon_dtype)
+[[maybe_unused]] static bool h16_dtype(int dtype) { return dtype == BINE_FLOAT16 || dtype == BINE_BFLOAT16; }
 
 // the element type an op runs on (see kLogicT / kBitsT); *scale = elements
 // of the run type per element of `dtype`; -1: the op is not defined on the
-// type (bitwise ops on float / double: MPICH's MPI_ERR_OP)
+// type (bitwise ops on float / double: MPICH's MPI_ERR_OP; anything but the
+// arithmetic four on float16 / bfloat16, which otherwise pass through)
 static int canon_dtype(int dtype, int op, size_t *scale) {
   *scale = 1;
   if (!bine_op_valid(dtype, op)) return -1;
@@ -231,6 +258,35 @@ typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 template <typename T, int OP>
 __device__ __forceinline__ u32x4_t apply16(u32x4_t vb, u32x4_t va) {
   constexpr int N = 16 / (int)sizeof(T);
+  if constexpr (std::is_same_v<T, F16> && (OP == BINE_SUM || OP == BINE_PROD)) {
+    // 8 binary16 lanes: packed f16 add / mul (v_pk_add_f16 / v_pk_mul_f16)
+    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+    f16x8 b, a;
+    __builtin_memcpy(&b, &vb, 16);
+    __builtin_memcpy(&a, &va, 16);
+    b = OP == BINE_SUM ? b + a : b * a;
+    u32x4_t r;
+    __builtin_memcpy(&r, &b, 16);
+    return r;
+  } else if constexpr (std::is_same_v<T, BF16> && (OP == BINE_SUM || OP == BINE_PROD)) {
+    // 8 bfloat16 lanes: the even elements (low halves) widened by a shift,
+    // the odd ones by a mask, into two float4s; packed fp32 add / mul; one
+    // round-to-nearest-even conversion per pair (v_cvt_pk_bf16_f32: element
+    // 2k from the low-half result, 2k + 1 from the high-half result)
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+    const u32x4_t blo = vb << 16, bhi = vb & 0xffff0000u, alo = va << 16, ahi = va & 0xffff0000u;
+    f32x4 xl, xh, yl, yh;
+    __builtin_memcpy(&xl, &blo, 16);
+    __builtin_memcpy(&xh, &bhi, 16);
+    __builtin_memcpy(&yl, &alo, 16);
+    __builtin_memcpy(&yh, &ahi, 16);
+    const f32x4 lo = OP == BINE_SUM ? xl + yl : xl * yl, hi = OP == BINE_SUM ? xh + yh : xh * yh;
+    const bf16x8 h = __builtin_convertvector(__builtin_shufflevector(lo, hi, 0, 4, 1, 5, 2, 6, 3, 7), bf16x8);
+    u32x4_t r;
+    __builtin_memcpy(&r, &h, 16);
+    return r;
+  }
   T b[N], a[N];
   __builtin_memcpy(b, &vb, 16);
   __builtin_memcpy(a, &va, 16);
@@ -386,6 +442,7 @@ static hipError_t reduce_op(const void *a, const void *b, void *out, size_t n, i
 int BINE_FN(launch_reduce)(const void *a, const void *b, void *out, size_t count, int dtype, int op, void *stream) {
   if (count == 0) return BINE_SUCCESS;
 #if BINE_OPSET == 0
+  if (h16_dtype(dtype)) return launch_reduce_h16(a, b, out, count, dtype, op, stream);
   if (ext_op(dtype, op)) return launch_reduce_logic(a, b, out, count, dtype, op, stream);
 #endif
   size_t scale;
@@ -396,6 +453,10 @@ int BINE_FN(launch_reduce)(const void *a, const void *b, void *out, size_t count
   hipStream_t st = (hipStream_t)stream;
   hipError_t e;
   switch (dtype) {
+#if BINE_OPSET == 2
+    case BINE_FLOAT16: e = reduce_op<F16>(a, b, out, count, op, st); break;
+    case BINE_BFLOAT16: e = reduce_op<BF16>(a, b, out, count, op, st); break;
+#else
     case BINE_INT8: e = reduce_op<int8_t>(a, b, out, count, op, st); break;
     case BINE_UINT8: e = reduce_op<uint8_t>(a, b, out, count, op, st); break;
     case BINE_INT16: e = reduce_op<int16_t>(a, b, out, count, op, st); break;
@@ -406,6 +467,7 @@ int BINE_FN(launch_reduce)(const void *a, const void *b, void *out, size_t count
     case BINE_UINT64: e = reduce_op<uint64_t>(a, b, out, count, op, st); break;
     case BINE_FLOAT: e = reduce_op<float>(a, b, out, count, op, st); break;
     case BINE_DOUBLE: e = reduce_op<double>(a, b, out, count, op, st); break;
+#endif
 #if BINE_OPSET == 1
     case BINE_FLOAT_INT: e = reduce_op<Pair<float>>(a, b, out, count, op, st); break;
     case BINE_DOUBLE_INT: e = reduce_op<Pair<double>>(a, b, out, count, op, st); break;
@@ -563,6 +625,7 @@ int BINE_FN(launch_reduce_batch)(int n, const void *const *a, const void *const 
                                  const size_t *count_in, int dtype, int op, void *stream) {
   if (n < 1 || n > kMaxBatch) return BINE_ERR_ARG;
 #if BINE_OPSET == 0
+  if (h16_dtype(dtype)) return launch_reduce_batch_h16(n, a, b, out, count_in, dtype, op, stream);
   if (ext_op(dtype, op)) return launch_reduce_batch_logic(n, a, b, out, count_in, dtype, op, stream);
 #endif
   size_t scale;
@@ -573,6 +636,10 @@ int BINE_FN(launch_reduce_batch)(int n, const void *const *a, const void *const 
   hipStream_t st = (hipStream_t)stream;
   hipError_t e;
   switch (dtype) {
+#if BINE_OPSET == 2
+    case BINE_FLOAT16: e = batch_op<F16>(n, a, b, out, count, op, st); break;
+    case BINE_BFLOAT16: e = batch_op<BF16>(n, a, b, out, count, op, st); break;
+#else
     case BINE_INT8: e = batch_op<int8_t>(n, a, b, out, count, op, st); break;
     case BINE_UINT8: e = batch_op<uint8_t>(n, a, b, out, count, op, st); break;
     case BINE_INT16: e = batch_op<int16_t>(n, a, b, out, count, op, st); break;
@@ -583,6 +650,7 @@ int BINE_FN(launch_reduce_batch)(int n, const void *const *a, const void *const 
     case BINE_UINT64: e = batch_op<uint64_t>(n, a, b, out, count, op, st); break;
     case BINE_FLOAT: e = batch_op<float>(n, a, b, out, count, op, st); break;
     case BINE_DOUBLE: e = batch_op<double>(n, a, b, out, count, op, st); break;
+#endif
 #if BINE_OPSET == 1
     case BINE_FLOAT_INT: e = batch_op<Pair<float>>(n, a, b, out, count, op, st); break;
     case BINE_DOUBLE_INT: e = batch_op<Pair<double>>(n, a, b, out, count, op, st); break;
@@ -793,6 +861,7 @@ int BINE_FN(launch_reduce_tree)(int nl, const void *const *leaf, void *out, size
                                 void *stream, unsigned swap) {
   if (count == 0) return BINE_SUCCESS;
 #if BINE_OPSET == 0
+  if (h16_dtype(dtype)) return launch_reduce_tree_h16(nl, leaf, out, count, dtype, op, stream, swap);
   if (ext_op(dtype, op)) return launch_reduce_tree_logic(nl, leaf, out, count, dtype, op, stream, swap);
 #endif
   if (nl < 2 || nl > kMaxLeaves || (nl & (nl - 1))) return BINE_ERR_ARG;
@@ -807,6 +876,10 @@ int BINE_FN(launch_reduce_tree)(int nl, const void *const *leaf, void *out, size
   hipStream_t st = (hipStream_t)stream;
   hipError_t e;
   switch (dtype) {
+#if BINE_OPSET == 2
+    case BINE_FLOAT16: e = tree_op<F16>(nl, t, op, st); break;
+    case BINE_BFLOAT16: e = tree_op<BF16>(nl, t, op, st); break;
+#else
     case BINE_INT8: e = tree_op<int8_t>(nl, t, op, st); break;
     case BINE_UINT8: e = tree_op<uint8_t>(nl, t, op, st); break;
     case BINE_INT16: e = tree_op<int16_t>(nl, t, op, st); break;
@@ -817,6 +890,7 @@ int BINE_FN(launch_reduce_tree)(int nl, const void *const *leaf, void *out, size
     case BINE_UINT64: e = tree_op<uint64_t>(nl, t, op, st); break;
     case BINE_FLOAT: e = tree_op<float>(nl, t, op, st); break;
     case BINE_DOUBLE: e = tree_op<double>(nl, t, op, st); break;
+#endif
 #if BINE_OPSET == 1
     case BINE_FLOAT_INT: e = tree_op<Pair<float>>(nl, t, op, st); break;
     case BINE_DOUBLE_INT: e = tree_op<Pair<double>>(nl, t, op, st); break;
