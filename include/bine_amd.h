@@ -209,6 +209,44 @@ int bine_reduce_tree(int nleaves, const void *const *leaves, void *out, size_t c
 int bine_reduce_tree_swap(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
                           unsigned swap, void *stream);
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
+
+/* ---- scaled (averaging) reductions -------------------------------------------
+ * A scaled call returns S(R[i]) for every output element: R is exactly what
+ * the unscaled call (bine_allreduce / bine_reduce_scatter / bine_reduce_tree_swap)
+ * returns, bit for bit, for the same algorithm, arguments and communicator
+ * settings, and S is ONE multiplication by `scale` (a double), per element type:
+ *   BINE_FLOAT     S(x) = x * (float)scale; (float)scale is the round-to-
+ *                  nearest-even conversion, the product IEEE binary32, nearest even.
+ *   BINE_DOUBLE    S(x) = x * scale, IEEE binary64.
+ *   BINE_FLOAT16,  x is widened exactly to binary32 and multiplied by
+ *   BINE_BFLOAT16  (float)scale in binary32 (nearest even); that binary32 value
+ *                  is then rounded to nearest even into the 16-bit format.  TWO
+ *                  roundings, by definition.
+ * Subnormals are kept on input and output; a NaN result has an unspecified
+ * payload; `scale` may be any double (infinities and NaN follow IEEE).
+ * scale == 1.0 takes the unscaled path unchanged: no extra kernel, the same
+ * bits.  Valid for the four floating types with SUM, PROD, MAX and MIN (S is
+ * applied after the reduction whatever the op); every other (dtype, op) pair
+ * -- integers, pair types, complex, logical and bitwise ops -- is
+ * BINE_ERR_ARG, returned on every rank before any exchange and before any
+ * HIP call.  Two consequences: (1) for the 16-bit types the tree's last level
+ * still rounds to 16 bits before S -- S acts on the 16-bit reduced value, not
+ * on the binary32 intermediate of the last add; (2) the conversion back to
+ * binary16 rounds to nearest even, never toward zero.  The result is the same
+ * bit for bit in the literal and the flat forms: where the flat
+ * reduce-scatter's trees produce the final values the multiplication happens
+ * in the tree kernel's registers before the store (no extra pass over
+ * memory), elsewhere one in-place k_scale over the rank's output ends the
+ * call (BINE_PRIM_SCALED / BINE_PRIM_SCALE below).  Not provided: bine_reduce,
+ * the staged host-buffer entry points, the libbine.h drop-in. */
+/* 1 exactly on {FLOAT, DOUBLE, FLOAT16, BFLOAT16} x {SUM, PROD, MAX, MIN} */
+int bine_scale_valid(int dtype, int op);
+/* the arithmetic boundary: out[i] = S(in[i]); out == in allowed (otherwise
+ * the two must not overlap); any operand alignment bine_reduce3 accepts */
+int bine_scale(const void *in, void *out, size_t count, int dtype, double scale, void *stream);
+/* bine_reduce_tree_swap's result with S applied, in the same launch */
+int bine_reduce_tree_scaled(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
+                            unsigned swap, double scale, void *stream);
 /* copy_buffer on the device (libbine_utils.h:176-190; the sbuf -> rbuf copy of
  * e.g. allreduce_bine_bdw_remap, libbine_allreduce.c:849-852): dst[0:bytes) =
  * src[0:bytes), stream-ordered, the kernel every COPY primitive runs. */
@@ -520,6 +558,17 @@ int bine_allreduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, siz
 /* reduce_scatter_* (libbine.h:69-77) */
 int bine_reduce_scatter(bine_comm_t comm, int algo, const void *sbuf, void *rbuf,
                         const int *rcounts, int dtype, int op, void *stream);
+/* the scaled forms (see "scaled reductions" above): S(result of the call
+ * without `scale`).  Graph mode keys its graphs on `scale` too.  Over the
+ * direct transport a call whose trees run inside the transport's launches
+ * (k_dm_move_tree / k_dm_fused: those kernels have no epilogue) takes exactly
+ * the form of the unscaled call, followed by one k_scale over the output on
+ * the caller's stream; where the trees run as separate launches (pull copies:
+ * always so for the 16-bit types) the flagged trees scale. */
+int bine_allreduce_scaled(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
+                          int dtype, int op, double scale, size_t segsize, void *stream);
+int bine_reduce_scatter_scaled(bine_comm_t comm, int algo, const void *sbuf, void *rbuf,
+                               const int *rcounts, int dtype, int op, double scale, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -579,6 +628,13 @@ int bine_loopback_run_allreduce(bine_comm_t *comms, int nranks, int algo,
 int bine_loopback_run_reduce_scatter(bine_comm_t *comms, int nranks, int algo,
                                      const void *const *sbufs, void *const *rbufs,
                                      const int *rcounts, int dtype, int op, int *statuses);
+int bine_loopback_run_allreduce_scaled(bine_comm_t *comms, int nranks, int algo,
+                                       const void *const *sbufs, void *const *rbufs, size_t count,
+                                       int dtype, int op, double scale, size_t segsize, int *statuses);
+int bine_loopback_run_reduce_scatter_scaled(bine_comm_t *comms, int nranks, int algo,
+                                            const void *const *sbufs, void *const *rbufs,
+                                            const int *rcounts, int dtype, int op, double scale,
+                                            int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);
@@ -598,7 +654,9 @@ int bine_loopback_run_alltoall(bine_comm_t *comms, int nranks, int algo, const v
  * A plan is the ordered list of primitives one rank executes. */
 typedef enum { BINE_PRIM_SEND = 1, BINE_PRIM_RECV = 2, BINE_PRIM_REDUCE = 3,
                BINE_PRIM_REDUCE3 = 4, BINE_PRIM_COPY = 5,
-               BINE_PRIM_REDUCE_TREE = 6  /* flat reduce-scatter: see bine_comm_set_flat_rs */
+               BINE_PRIM_REDUCE_TREE = 6, /* flat reduce-scatter: see bine_comm_set_flat_rs */
+               BINE_PRIM_SCALE = 7        /* scaled calls: dst_buf[dst_off, dst_off + count) scaled in
+                                             place (src = dst), on the caller's stream, last */
 } bine_prim_type_t;
 typedef enum { BINE_BUF_SBUF = 0, BINE_BUF_RBUF = 1, BINE_BUF_TMP0 = 2, BINE_BUF_TMP1 = 3,
                BINE_BUF_TMP2 = 4,
@@ -607,13 +665,16 @@ typedef enum { BINE_BUF_SBUF = 0, BINE_BUF_RBUF = 1, BINE_BUF_TMP0 = 2, BINE_BUF
 #define BINE_PRIM_PIPELINE 1  /* flags: exchange whose receive feeds the next
                                  REDUCE(3) element for element -- both may be
                                  split into chunks and overlapped */
+#define BINE_PRIM_SCALED 2    /* flags, REDUCE_TREE of a scaled call: the tree's output is
+                                 final and is multiplied by the call's scale before
+                                 it is stored */
 /* REDUCE_TREE: flags >> 8 = levels whose combine is v[i + w] (op) v[i] (the
    right subtree is the inout side; block_by_block's last step) */
 typedef struct {
   int32_t type;      /* bine_prim_type_t */
   int32_t group;     /* consecutive SEND/RECV with equal group form one exchange */
   int32_t peer;      /* SEND/RECV peer rank; REDUCE_TREE: number of leaves nl */
-  int32_t flags;     /* BINE_PRIM_PIPELINE */
+  int32_t flags;     /* BINE_PRIM_PIPELINE, BINE_PRIM_SCALED */
   int32_t src_buf;   /* SEND: source; REDUCE/REDUCE3: `in` (a); COPY: source;
                         REDUCE_TREE: the other nl-1 leaves, k-th at src_off + k*count */
   int32_t dst_buf;   /* RECV: destination; REDUCE: inout; REDUCE3 / REDUCE_TREE: out; COPY: dest */
@@ -647,8 +708,22 @@ int64_t bine_plan(int algo, int nranks, int rank, size_t count, const int *rcoun
  * bit 0 = multi-tree mode (bine_comm_set_trees), bit 1 = flat allgather
  * (bine_comm_set_flat_ag), bit 2 = flat reduce-scatter (bine_comm_set_flat_rs),
  * bit 3 = the allgather cut with the flat reduce-scatter's chunks
- * (bine_comm_set_flat_ag(2)).  Returns the number of entries (may exceed cap)
- * or -status. */
+ * (bine_comm_set_flat_ag(2)), bit 4 (16) = the call is scaled
+ * (bine_allreduce_scaled / bine_reduce_scatter_scaled).  A scaled schedule
+ * equals the unscaled one op for op and wait for wait, except that either
+ * every REDUCE_TREE whose output is final carries BINE_PRIM_SCALED (the flat
+ * reduce-scatter forms at power-of-two P <= 16; chunked copies of a tree
+ * inherit the flag) or, where no such tree covers the rank's output (literal
+ * schedules, the rings' folded chain, non-power-of-two P, multi-tree mode,
+ * P = 1), exactly one trailing BINE_PRIM_SCALE over the rank's output -- RBUF
+ * [0, count) for an allreduce, [0, rcounts[rank]) for a reduce-scatter -- on
+ * the caller's stream after everything else: every output element is scaled
+ * exactly once.  (At P = 1 out of place the executor runs the COPY + SCALE
+ * pair as one out-of-place k_scale.)  This is the RCCL / loopback form; over
+ * the direct transport a call whose trees run inside the transport's
+ * launches runs the unscaled schedule plus a trailing scale.  Without bit 4
+ * the output is what it always was.  Returns the number of entries (may
+ * exceed cap) or -status. */
 typedef struct {
   int32_t op;
   int32_t xchg;

@@ -10,6 +10,12 @@ Element types: ``DTYPES`` are MPICH's 17 reduction types (the reference's);
 ``EXT_DTYPES`` adds "float16" and "bfloat16" (torch.float16 / torch.bfloat16),
 reduced under sum / prod / max / min with every pairwise result correctly
 rounded to the 16-bit format.
+
+Scaled (averaging) forms: ``allreduce(..., scale=s)`` / ``reduce_scatter(...,
+scale=s)`` return the unscaled call's bits times ``s`` (one multiplication per
+element, defined in include/bine_amd.h), ``op="avg"`` is ``op="sum",
+scale=1/comm.size``; floating types with sum / prod / max / min.  ``scale()``
+is the arithmetic on its own.
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

@@ -74,7 +74,9 @@ class OpTime(ctypes.Structure):
                 ("start_ms", ctypes.c_float), ("ms", ctypes.c_float)]
 
 
-PRIM_NAMES = {1: "SEND", 2: "RECV", 3: "REDUCE", 4: "REDUCE3", 5: "COPY", 6: "REDUCE_TREE"}
+PRIM_NAMES = {1: "SEND", 2: "RECV", 3: "REDUCE", 4: "REDUCE3", 5: "COPY", 6: "REDUCE_TREE", 7: "SCALE"}
+# bine_prim_t.flags
+PRIM_PIPELINE, PRIM_SCALED = 1, 2
 
 
 class BineError(RuntimeError):
@@ -149,6 +151,13 @@ def lib():
         "bine_reduce_batch": ([i, vp, vp, vp, vp, i, i, vp], i),
         "bine_reduce_tree": ([i, vp, vp, ctypes.c_size_t, i, i, vp], i),
         "bine_reduce_tree_swap": ([i, vp, vp, ctypes.c_size_t, i, i, ctypes.c_uint, vp], i),
+        "bine_scale_valid": ([i, i], i),
+        "bine_scale": ([vp, vp, sz, i, ctypes.c_double, vp], i),
+        "bine_reduce_tree_scaled": ([i, vp, vp, sz, i, i, ctypes.c_uint, ctypes.c_double, vp], i),
+        "bine_allreduce_scaled": ([vp, i, vp, vp, sz, i, i, ctypes.c_double, sz, vp], i),
+        "bine_reduce_scatter_scaled": ([vp, i, vp, vp, vp, i, i, ctypes.c_double, vp], i),
+        "bine_loopback_run_allreduce_scaled": ([vp, i, i, vp, vp, sz, i, i, ctypes.c_double, sz, vp], i),
+        "bine_loopback_run_reduce_scatter_scaled": ([vp, i, i, vp, vp, vp, i, i, ctypes.c_double, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

@@ -314,13 +314,55 @@ def _algo(coll: str, algo) -> int:
     return algo if isinstance(algo, int) else ALGOS[coll][algo]
 
 
-def allreduce(algo, sbuf, rbuf, count: int, dtype, op: str, comm: Comm, segsize: int = 0, stream=None) -> None:
+def _scaled(op: str, scale, comm: Comm):
+    """(op, scale) of a call: op="avg" is op="sum" with scale = 1 / comm.size
+    (resolved here; the C op table has no such op)."""
+    if op == "avg":
+        if scale is not None:
+            raise ValueError('op="avg" is op="sum", scale=1/comm.size: pass no scale of your own')
+        return "sum", 1.0 / comm.size
+    return op, scale
+
+
+def scale(inbuf, outbuf, count: int, dtype=None, scale: float = 1.0, stream=None) -> None:
+    """out[i] = S(in[i]) (bine_scale): one multiplication by `scale` as the
+    scaled collectives define it -- float / double in their own format; float16
+    / bfloat16 widened to binary32, multiplied by float32(scale), rounded to
+    nearest even.  outbuf may be inbuf."""
+    check(lib().bine_scale(_ptr(inbuf), _ptr(outbuf), count, _dtype(dtype, outbuf), float(scale),
+                           _stream(stream, None)), "bine_scale")
+
+
+def scale_valid(dtype, op: str) -> bool:
+    """whether the scaled calls accept (dtype, op): the four floating types
+    with sum / prod / max / min (bine_scale_valid)"""
+    return bool(lib().bine_scale_valid(_dtype(dtype), OPS[op]))
+
+
+def allreduce(algo, sbuf, rbuf, count: int, dtype, op: str, comm: Comm, segsize: int = 0, stream=None,
+              scale=None) -> None:
+    """scale: the result times `scale` (bine_allreduce_scaled; op="avg": the
+    mean, sum times 1 / comm.size), fused into the flat forms' tree kernels"""
+    op, scale = _scaled(op, scale, comm)
+    if scale is not None:
+        check(lib().bine_allreduce_scaled(comm.handle, _algo("allreduce", algo), _ptr(sbuf), _ptr(rbuf), count,
+                                          _dtype(dtype, rbuf), OPS[op], float(scale), segsize,
+                                          _stream(stream, comm)), f"allreduce_{algo} (scaled)")
+        return
     check(lib().bine_allreduce(comm.handle, _algo("allreduce", algo), _ptr(sbuf), _ptr(rbuf), count,
                                _dtype(dtype, rbuf), OPS[op], segsize, _stream(stream, comm)), f"allreduce_{algo}")
 
 
-def reduce_scatter(algo, sbuf, rbuf, rcounts: Sequence[int], dtype, op: str, comm: Comm, stream=None) -> None:
+def reduce_scatter(algo, sbuf, rbuf, rcounts: Sequence[int], dtype, op: str, comm: Comm, stream=None,
+                   scale=None) -> None:
+    """scale: as allreduce's (bine_reduce_scatter_scaled)"""
     rc = (ctypes.c_int * len(rcounts))(*rcounts)
+    op, scale = _scaled(op, scale, comm)
+    if scale is not None:
+        check(lib().bine_reduce_scatter_scaled(comm.handle, _algo("reduce_scatter", algo), _ptr(sbuf), _ptr(rbuf),
+                                               rc, _dtype(dtype, rbuf), OPS[op], float(scale),
+                                               _stream(stream, comm)), f"reduce_scatter_{algo} (scaled)")
+        return
     check(lib().bine_reduce_scatter(comm.handle, _algo("reduce_scatter", algo), _ptr(sbuf), _ptr(rbuf), rc,
                                     _dtype(dtype, rbuf), OPS[op], _stream(stream, comm)), f"reduce_scatter_{algo}")
 
@@ -359,18 +401,30 @@ def _ptrs(bufs):
     return (ctypes.c_void_p * len(bufs))(*[_ptr(b) for b in bufs])
 
 
-def loopback_allreduce(comms, algo, sbufs, rbufs, count, dtype, op="sum", segsize=0):
+def loopback_allreduce(comms, algo, sbufs, rbufs, count, dtype, op="sum", segsize=0, scale=None):
     st = (ctypes.c_int * len(comms))()
     hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
+    op, scale = _scaled(op, scale, comms[0])
+    if scale is not None:
+        rc = lib().bine_loopback_run_allreduce_scaled(hs, len(comms), _algo("allreduce", algo), _ptrs(sbufs),
+                                                      _ptrs(rbufs), count, _dtype(dtype, rbufs[0]), OPS[op],
+                                                      float(scale), segsize, st)
+        return rc, list(st)
     rc = lib().bine_loopback_run_allreduce(hs, len(comms), _algo("allreduce", algo), _ptrs(sbufs), _ptrs(rbufs),
                                            count, _dtype(dtype, rbufs[0]), OPS[op], segsize, st)
     return rc, list(st)
 
 
-def loopback_reduce_scatter(comms, algo, sbufs, rbufs, rcounts, dtype, op="sum"):
+def loopback_reduce_scatter(comms, algo, sbufs, rbufs, rcounts, dtype, op="sum", scale=None):
     st = (ctypes.c_int * len(comms))()
     hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
     rcs = (ctypes.c_int * len(rcounts))(*rcounts)
+    op, scale = _scaled(op, scale, comms[0])
+    if scale is not None:
+        rc = lib().bine_loopback_run_reduce_scatter_scaled(hs, len(comms), _algo("reduce_scatter", algo),
+                                                           _ptrs(sbufs), _ptrs(rbufs), rcs,
+                                                           _dtype(dtype, rbufs[0]), OPS[op], float(scale), st)
+        return rc, list(st)
     rc = lib().bine_loopback_run_reduce_scatter(hs, len(comms), _algo("reduce_scatter", algo), _ptrs(sbufs),
                                                 _ptrs(rbufs), rcs, _dtype(dtype, rbufs[0]), OPS[op], st)
     return rc, list(st)
@@ -407,15 +461,18 @@ def plan(coll: str, algo, nranks: int, rank: int, count: int = 0, rcounts=None, 
 def schedule(coll: str, algo, nranks: int, rank: int, count: int = 0, rcounts=None, root: int = 0,
              esz: int = 4, segsize: int = 0, in_place: bool = False, chunk_bytes: int = 0,
              relay_min_bytes: int = 0, info: bool = False, trees: bool = False, flat_ag: bool = False,
-             flat_rs: bool = False):
+             flat_rs: bool = False, scaled: bool = False):
     """The executor's two-stream issue schedule of rank `rank` (host only).
+    scaled=True: of the scaled call (flagged trees, flags & PRIM_SCALED, or one
+    trailing "SCALE").
     Returns (ops, c_join, final_wait); ops[i] = {"xchg", "wait", "prims"}.
     With info=True a 4th item: {"tmp_elems": [TMP0..2], "stage_elems": relay staging}."""
     a = _algo(coll, algo)
     rc = (ctypes.c_int * nranks)(*(rcounts or [0] * nranks))
     cj, fw, ws = ctypes.c_int(), ctypes.c_int64(), (ctypes.c_uint64 * 4)()
     args = (a, nranks, rank, count, rc, root, esz, segsize, int(in_place), chunk_bytes, relay_min_bytes,
-            int(trees) | (2 if flat_ag else 0) | (4 if flat_rs else 0) | (8 if flat_ag == 2 else 0))
+            int(trees) | (2 if flat_ag else 0) | (4 if flat_rs else 0) | (8 if flat_ag == 2 else 0) |
+            (16 if scaled else 0))
     n = lib().bine_plan_schedule(*args, None, 0, ctypes.byref(cj), ctypes.byref(fw), ws)
     if n < 0:
         raise BineError(int(-n), f"schedule {coll}_{algo}")
@@ -526,11 +583,15 @@ def reduce_batch(ins, inouts, counts, dtype, op: str = "sum", stream=None) -> in
     return lib().bine_reduce_batch(n, _ptrs(ins), b, b, c, _dtype(dtype, inouts[0]), OPS[op], _stream(stream, None))
 
 
-def reduce_tree(leaves, out, count: int, dtype, op: str = "sum", stream=None, swap: int = 0) -> int:
+def reduce_tree(leaves, out, count: int, dtype, op: str = "sum", stream=None, swap: int = 0, scale=None) -> int:
     """out[:count] = the reduction tree over the leaf buffers (tree order,
     len 2/4/8/16) in one launch (bine_reduce_tree; bit l of `swap`: level l
-    takes its right operand as the inout side, bine_reduce_tree_swap).
+    takes its right operand as the inout side, bine_reduce_tree_swap; scale:
+    the result times `scale` in the same launch, bine_reduce_tree_scaled).
     Returns the status."""
+    if scale is not None:
+        return lib().bine_reduce_tree_scaled(len(leaves), _ptrs(leaves), _ptr(out), count, _dtype(dtype, out),
+                                             OPS[op], swap, float(scale), _stream(stream, None))
     if swap:
         return lib().bine_reduce_tree_swap(len(leaves), _ptrs(leaves), _ptr(out), count, _dtype(dtype, out),
                                            OPS[op], swap, _stream(stream, None))
@@ -631,16 +692,16 @@ def loopback_alltoall(comms, algo, sbufs, rbufs, count, dtype):
 # ---- libbine-named entry points (include/libbine.h:30-78) --------------------------
 
 def _mk_ar(name):
-    def f(sbuf, rbuf, count, dtype, op, comm, stream=None, segsize: int = 0):
-        allreduce(name, sbuf, rbuf, count, dtype, op, comm, segsize=segsize, stream=stream)
+    def f(sbuf, rbuf, count, dtype, op, comm, stream=None, segsize: int = 0, scale=None):
+        allreduce(name, sbuf, rbuf, count, dtype, op, comm, segsize=segsize, stream=stream, scale=scale)
     f.__name__ = "allreduce_" + name
     f.__doc__ = f"allreduce_{name} (libbine_allreduce.c) on MI355X."
     return f
 
 
 def _mk_rs(name):
-    def f(sbuf, rbuf, rcounts, dtype, op, comm, stream=None):
-        reduce_scatter(name, sbuf, rbuf, rcounts, dtype, op, comm, stream=stream)
+    def f(sbuf, rbuf, rcounts, dtype, op, comm, stream=None, scale=None):
+        reduce_scatter(name, sbuf, rbuf, rcounts, dtype, op, comm, stream=stream, scale=scale)
     f.__name__ = "reduce_scatter_" + name
     f.__doc__ = f"reduce_scatter_{name} (libbine_reduce_scatter.c) on MI355X."
     return f
@@ -690,7 +751,7 @@ ENTRY_POINTS["scatter_bine"] = lambda sbuf, rbuf, count, dtype, root, comm, stre
 globals().update(ENTRY_POINTS)
 
 __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fused_msgs", "reduce_local", "reduce3", "fill_pico", "checksum", "copy",
-           "rccl_version",
+           "rccl_version", "scale", "scale_valid",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

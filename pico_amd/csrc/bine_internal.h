@@ -19,6 +19,7 @@ struct Plan {
   std::vector<Prim> prims;
   uint64_t tmp_elems[3] = {0, 0, 0};  // workspace per TMP buffer, elements
   int status = BINE_SUCCESS;          // non-success: the reference's error return
+  bool scale_fused = false;           // scaled call: the flagged trees scale, no trailing SCALE
 };
 
 struct PlanArgs {
@@ -52,9 +53,23 @@ struct PlanArgs {
   // host-buffer pipeline copies each chunk back as soon as it is final).  Pure
   // data movement: result bits unchanged.
   bool flat_ag_chunked = false;
+  // scaled call (bine_allreduce_scaled / bine_reduce_scatter_scaled): every
+  // element of this rank's output is multiplied by the call's scale exactly
+  // once.  Where the flat reduce-scatter's trees produce the final values
+  // (flat_rs(): the per-block trees of the bandwidth allreduces and of the
+  // reduce-scatters, the one-shot trees of allreduce_bine_lat /
+  // _recursivedoubling) they carry BINE_PRIM_SCALED and scale in registers
+  // before their store; whatever moves their output afterwards (the allgather
+  // phase, the in-place copy) moves scaled data.  Everywhere else -- literal
+  // schedules, the rings' folded chain, non-power-of-two P, multi-tree mode,
+  // P = 1 -- the plan ends with one BINE_PRIM_SCALE over the rank's output.
+  // Which of the two a call gets depends on (algorithm, P, counts, forms)
+  // alone, never on the rank: no element is scaled twice or not at all.
+  bool scaled = false;
 };
 
 Plan make_plan(const PlanArgs &a);
+void append_scale(Plan &p, const PlanArgs &a);  // the trailing SCALE of a scaled call (unless p.scale_fused)
 
 // multi-tree mode (trees.cpp): P-1 relabelled instances on P-1 slices; status
 // BINE_ERR_UNSUPPORTED when not applicable (only allreduce, P = 4 or 8)
@@ -151,6 +166,16 @@ int launch_reduce_batch_h16(int n, const void *const *a, const void *const *b, v
                             const size_t *count, int dtype, int op, void *stream);
 int launch_reduce_tree_h16(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
                            void *stream, unsigned swap);
+// out[i] = S(in[i]) (k_scale; in == out allowed) and the tree with S applied
+// to its result in the same launch (k_reduce_tree_sc): float / double in the
+// opset-0 compilation, float16 / bfloat16 in opset 2.  BINE_ERR_ARG unless
+// bine_scale_valid(dtype, op).
+int launch_scale(const void *in, void *out, size_t count, int dtype, double scale, void *stream);
+int launch_scale_h16(const void *in, void *out, size_t count, int dtype, double scale, void *stream);
+int launch_reduce_tree_scaled(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
+                              void *stream, unsigned swap, double scale);
+int launch_reduce_tree_scaled_h16(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
+                                  void *stream, unsigned swap, double scale);
 // copy_buffer on the device (k_copy); hipMemcpyAsync when src / dst are not
 // co-aligned mod 16 B
 int launch_copy(void *dst, const void *src, size_t bytes, void *stream);

@@ -521,6 +521,7 @@ struct bine_comm {
   std::vector<char> tree_pending;
   // per-op device timing of the latest collective (bine_comm_set_profile)
   bool profile = false;
+  double call_scale = 1.0;  // the scale of the scaled call being issued (under mu; flagged trees, SCALE)
   struct OpTime { hipEvent_t a = nullptr, b = nullptr; int xchg = 0, nprims = 0; uint64_t bytes = 0; };
   std::vector<OpTime> prof;
   size_t prof_n = 0;
@@ -766,7 +767,8 @@ static size_t default_chunk_bytes(bool direct) {
 // the local primitives of one op: several reductions go out as one batched
 // launch (multi-tree rounds), anything else one launch / copy each
 template <typename Ptr>
-static int run_local(const std::vector<Prim> &prims, Ptr ptr, int dtype, int op, size_t esz, hipStream_t K) {
+static int run_local(const std::vector<Prim> &prims, Ptr ptr, int dtype, int op, size_t esz, hipStream_t K,
+                     double scale = 1.0) {
   const size_t n = prims.size();
   bool batch = n >= 2 && n <= (size_t)kMaxBatch;
   for (const Prim &p : prims) batch = batch && (p.type == BINE_PRIM_REDUCE || p.type == BINE_PRIM_REDUCE3);
@@ -795,9 +797,15 @@ static int run_local(const std::vector<Prim> &prims, Ptr ptr, int dtype, int op,
       const void *leaf[kMaxLeaves];
       for (int j = 0, k = 0; j < p.peer; j++)
         leaf[j] = j == p.pos ? ptr(p.aux_buf, p.aux_off) : ptr(p.src_buf, p.src_off + (uint64_t)k++ * p.count);
-      rc = launch_reduce_tree(p.peer, leaf, ptr(p.dst_buf, p.dst_off), p.count, dtype, op, K,
-                              (unsigned)p.flags >> 8);
-    } else if (p.type == BINE_PRIM_REDUCE3)
+      if (p.flags & BINE_PRIM_SCALED)  // a scaled call's final tree: S in the same launch
+        rc = launch_reduce_tree_scaled(p.peer, leaf, ptr(p.dst_buf, p.dst_off), p.count, dtype, op, K,
+                                       (unsigned)p.flags >> 8, scale);
+      else
+        rc = launch_reduce_tree(p.peer, leaf, ptr(p.dst_buf, p.dst_off), p.count, dtype, op, K,
+                                (unsigned)p.flags >> 8);
+    } else if (p.type == BINE_PRIM_SCALE)
+      rc = launch_scale(ptr(p.src_buf, p.src_off), ptr(p.dst_buf, p.dst_off), p.count, dtype, scale, K);
+    else if (p.type == BINE_PRIM_REDUCE3)
       rc = launch_reduce(ptr(p.src_buf, p.src_off), ptr(p.aux_buf, p.aux_off), ptr(p.dst_buf, p.dst_off), p.count,
                          dtype, op, K);
     else
@@ -890,6 +898,7 @@ static bool build_fused(const FusedEnv &e, OpSpan ops, Ptr ptr, size_t esz, int 
   size_t C = 0, i = 0;
   while (i + 1 < nops && ops[i].xchg && !ops[i + 1].xchg) {
     if (ops[i + 1].prims.size() != 1 || ops[i + 1].prims[0].type != BINE_PRIM_REDUCE_TREE) return false;
+    if (ops[i + 1].prims[0].flags & BINE_PRIM_SCALED) return false;  // k_dm_fused has no scale epilogue
     C++;
     i += 2;
   }
@@ -1187,6 +1196,7 @@ static bool plan_dm_trees(const Transport &tx, bool on, const Schedule &sc, Ptr 
         sc.ops[j].prims[0].type != BINE_PRIM_REDUCE_TREE)
       continue;
     const Prim &t = sc.ops[j].prims[0];
+    if (t.flags & BINE_PRIM_SCALED) continue;  // k_dm_move_tree has no scale epilogue: a separate launch
     // the staging buffer: only receives write it, only trees read it
     if (t.src_buf < 0 || t.src_buf >= 8 || !clean_buf[t.src_buf]) continue;
     TreeSpec ts;
@@ -1324,7 +1334,7 @@ static int execute(bine_comm *c, const Schedule &sc, const void *sbuf, void *rbu
       if (x.type == BINE_PRIM_SEND) pt.bytes += x.count * esz;
       else if (x.type == BINE_PRIM_REDUCE || x.type == BINE_PRIM_REDUCE3) pt.bytes += 3 * x.count * esz;
       else if (x.type == BINE_PRIM_REDUCE_TREE) pt.bytes += (uint64_t)(x.peer + 1) * x.count * esz;
-      else if (x.type == BINE_PRIM_COPY) pt.bytes += 2 * x.count * esz;
+      else if (x.type == BINE_PRIM_COPY || x.type == BINE_PRIM_SCALE) pt.bytes += 2 * x.count * esz;
     }
     HIP_TRY(hipEventRecord(pt.a, s));
     return BINE_SUCCESS;
@@ -1457,7 +1467,7 @@ static int execute(bine_comm *c, const Schedule &sc, const void *sbuf, void *rbu
       }
       if (rc) return rc;
     } else {
-      rc = run_local(o.prims, ptr, dtype, op, esz, K);
+      rc = run_local(o.prims, ptr, dtype, op, esz, K, c->call_scale);
       if (rc) { set_err("local primitive failed (%s)", bine_status_string(rc)); return rc; }
     }
     if (prof)
@@ -1500,6 +1510,7 @@ static std::string plan_key(const PlanArgs &a) {
   snprintf(buf, sizeof buf, "%d|%zu|%zu|%zu|%d|%d|%d|%d|%d|", a.algo, a.count, a.esz, a.segsize, (int)a.in_place,
            a.root, (int)a.flat_ag, (int)a.flat_ag_chunked, (int)a.flat_rs);
   k = buf;
+  if (a.scaled) k += "S|";
   for (int x : a.rcounts) { k += std::to_string(x); k += ','; }
   return k;
 }
@@ -1695,8 +1706,12 @@ constexpr int kOpNone = -1;
 // `stg` (host staging, bine_*_staged): the flat forms are forced on for the
 // call (bit-identical; the allgather cut with the reduce-scatter's chunks, so
 // the output completes chunk by chunk), never graph-captured
+// `scale` (bine_*_scaled): the call returns S(result) -- through the scaled
+// plan (PlanArgs::scaled: flagged trees or a trailing SCALE), or, over the
+// direct transport where the trees run inside its launches, through the
+// unscaled call's very form followed by one k_scale over the output on K
 static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbuf, int dtype, int op,
-                          size_t chunk_bytes, void *stream, Staging *stg = nullptr) {
+                          size_t chunk_bytes, void *stream, Staging *stg = nullptr, const double *scale = nullptr) {
   if (!c) return BINE_ERR_ARG;
   if (dtype < 0 || (dtype >= BINE_NUM_DTYPES && !ext_dtype(dtype))) return BINE_ERR_UNSUPPORTED;
   if (op != kOpNone) {
@@ -1718,6 +1733,14 @@ static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbu
   a.flat_ag = c->flat_ag != 0 || stg;
   a.flat_ag_chunked = c->flat_ag == 2 || stg;
   a.flat_rs = c->flat_rs || stg;
+  bool post_scale = false;
+  if (scale) {
+    const auto *rt = dynamic_cast<const RcclTransport *>(c->tx.get());
+    post_scale = rt && rt->dm_on && rt->dm && c->dm_tree &&
+                 (dm_fused_supported(dtype, op) || dm_tree_supported(dtype, op, c->size));
+    a.scaled = !post_scale;
+  }
+  c->call_scale = scale ? *scale : 1.0;
   const size_t ch = chunk_elems(chunk_bytes, a.esz);
   const std::string key = plan_key(a) + "|" + std::to_string(ch) + "|" + std::to_string(c->relay_min_bytes) +
                           (c->trees ? "|T" : "");
@@ -1725,6 +1748,21 @@ static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbu
   if (it == c->plans.end()) {
     std::pair<Plan, Schedule> v;
     build(a, ch, c->relay_min_bytes, c->trees, v.first, v.second);
+    // one rank, out of place: the sbuf -> rbuf COPY and the trailing SCALE of
+    // the same range run as ONE out-of-place k_scale
+    std::vector<SOp> &ops = v.second.ops;
+    if (a.scaled && ops.size() == 2 && !ops[0].xchg && !ops[1].xchg && ops[0].prims.size() == 1 &&
+        ops[1].prims.size() == 1) {
+      const Prim &cp = ops[0].prims[0], &sp = ops[1].prims[0];
+      if (cp.type == BINE_PRIM_COPY && sp.type == BINE_PRIM_SCALE && cp.dst_buf == sp.dst_buf &&
+          cp.dst_off == sp.dst_off && cp.count == sp.count) {
+        Prim m = sp;
+        m.src_buf = cp.src_buf;
+        m.src_off = cp.src_off;
+        ops.assign(1, SOp{false, {m}, -1});
+        v.second.signals.assign(1, 0);
+      }
+    }
     it = c->plans.emplace(key, std::move(v)).first;
   }
   const Plan &plan = it->second.first;
@@ -1769,10 +1807,23 @@ static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbu
   if (rc) {
   } else if (c->graphs && K && !c->hub && !c->profile && !roctx_on() && !trace_on() && !stg &&
              (multi_branch_graphs_ok() ||
-              ((single || fused || (tpl && tpl->solo)) && hw_queues() >= (rccl_free(c) ? 2 : 4))))
-    rc = run_graph(c, key, sc, src, rbuf, a.esz, dtype, op, K, single, tpl, fused);
-  else
+              ((single || fused || (tpl && tpl->solo)) && hw_queues() >= (rccl_free(c) ? 2 : 4)))) {
+    // a captured flagged tree or SCALE carries its multiplier: the scale's bits
+    // are part of the graph's key
+    std::string gkey = key;
+    if (a.scaled) {
+      uint64_t bits;
+      memcpy(&bits, scale, sizeof bits);
+      gkey += "|x" + std::to_string(bits);
+    }
+    rc = run_graph(c, gkey, sc, src, rbuf, a.esz, dtype, op, K, single, tpl, fused);
+  } else
     rc = execute(c, sc, src, rbuf, a.esz, dtype, op, K, single, false, stg, tpl, fused);
+  if (!rc && post_scale) {  // after the final wait: K already follows the call's last exchange
+    const bool rs = a.algo >= BINE_RS_RECURSIVEHALVING && a.algo <= BINE_RS_BINE_BLOCK_BY_BLOCK_ANY_EVEN;
+    const size_t n = rs ? (size_t)a.rcounts[(size_t)a.rank] : a.count;
+    rc = launch_scale(rbuf, rbuf, n, dtype, *scale, K);
+  }
   if (!rc) rc = order_end(c, K);
   if (roctx_on()) roctxRangePop();
   return rc;
@@ -1939,6 +1990,24 @@ int bine_reduce_tree_swap(int nleaves, const void *const *leaves, void *out, siz
                           unsigned swap, void *stream) {
   if (!leaves || (!out && count)) return BINE_ERR_ARG;
   return launch_reduce_tree(nleaves, leaves, out, count, dtype, op, stream, swap);
+}
+
+int bine_scale_valid(int dtype, int op) {
+  const bool t = dtype == BINE_FLOAT || dtype == BINE_DOUBLE || dtype == BINE_FLOAT16 || dtype == BINE_BFLOAT16;
+  return t && op >= BINE_SUM && op <= BINE_MIN ? 1 : 0;
+}
+
+int bine_scale(const void *in, void *out, size_t count, int dtype, double scale, void *stream) {
+  if (!bine_scale_valid(dtype, BINE_SUM)) return BINE_ERR_ARG;
+  if (count && (!in || !out)) return BINE_ERR_ARG;
+  return launch_scale(in, out, count, dtype, scale, stream);
+}
+
+int bine_reduce_tree_scaled(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
+                            unsigned swap, double scale, void *stream) {
+  if (!bine_scale_valid(dtype, op)) return BINE_ERR_ARG;
+  if (nleaves < 2 || nleaves > kMaxLeaves || (nleaves & (nleaves - 1))) return BINE_ERR_ARG;
+  return launch_reduce_tree_scaled(nleaves, leaves, out, count, dtype, op, stream, swap, scale);
 }
 
 int bine_copy(void *dst, const void *src, size_t bytes, void *stream) {
@@ -2144,6 +2213,33 @@ int bine_reduce_scatter(bine_comm_t c, int algo, const void *sbuf, void *rbuf, c
   return run_collective(c, a, sbuf, rbuf, dtype, op, kCommChunk, stream);
 }
 
+// scaled forms: the pair is checked first, on every rank alike, before any
+// exchange and any HIP call; scale == 1.0 is the unscaled call itself
+int bine_allreduce_scaled(bine_comm_t c, int algo, const void *sbuf, void *rbuf, size_t count, int dtype, int op,
+                          double scale, size_t segsize, void *stream) {
+  if (!bine_scale_valid(dtype, op)) return BINE_ERR_ARG;
+  if (scale == 1.0) return bine_allreduce(c, algo, sbuf, rbuf, count, dtype, op, segsize, stream);
+  if (algo < BINE_AR_RECURSIVEDOUBLING || algo > BINE_AR_BINE_BLOCK_BY_BLOCK_ANY_EVEN) return BINE_ERR_UNSUPPORTED;
+  PlanArgs a;
+  a.algo = algo;
+  a.count = count;
+  a.segsize = segsize;
+  size_t chunk = algo == BINE_AR_BINE_BDW_REMAP_SEGMENTED ? segsize : (segsize ? segsize : kCommChunk);
+  return run_collective(c, a, sbuf, rbuf, dtype, op, chunk, stream, nullptr, &scale);
+}
+
+int bine_reduce_scatter_scaled(bine_comm_t c, int algo, const void *sbuf, void *rbuf, const int *rcounts, int dtype,
+                               int op, double scale, void *stream) {
+  if (!bine_scale_valid(dtype, op)) return BINE_ERR_ARG;
+  if (scale == 1.0) return bine_reduce_scatter(c, algo, sbuf, rbuf, rcounts, dtype, op, stream);
+  if (algo < BINE_RS_RECURSIVEHALVING || algo > BINE_RS_BINE_BLOCK_BY_BLOCK_ANY_EVEN) return BINE_ERR_UNSUPPORTED;
+  if (!c || !rcounts) return BINE_ERR_ARG;
+  PlanArgs a;
+  a.algo = algo;
+  a.rcounts.assign(rcounts, rcounts + c->size);
+  return run_collective(c, a, sbuf, rbuf, dtype, op, kCommChunk, stream, nullptr, &scale);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -2318,6 +2414,34 @@ int bine_loopback_run_reduce_scatter(bine_comm_t *comms, int n, int algo, const 
   });
 }
 
+int bine_loopback_run_allreduce_scaled(bine_comm_t *comms, int n, int algo, const void *const *sbufs,
+                                       void *const *rbufs, size_t count, int dtype, int op, double scale,
+                                       size_t segsize, int *statuses) {
+  if (!bine_scale_valid(dtype, op)) {  // before any thread, stream or HIP call
+    for (int r = 0; statuses && r < n; r++) statuses[r] = BINE_ERR_ARG;
+    return BINE_ERR_ARG;
+  }
+  return run_threads(comms, n, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_allreduce_scaled(comms[r], algo, sbufs[r], rbufs[r], count, dtype, op, scale, segsize,
+                                 comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_reduce_scatter_scaled(bine_comm_t *comms, int n, int algo, const void *const *sbufs,
+                                            void *const *rbufs, const int *rcounts, int dtype, int op, double scale,
+                                            int *statuses) {
+  if (!bine_scale_valid(dtype, op)) {
+    for (int r = 0; statuses && r < n; r++) statuses[r] = BINE_ERR_ARG;
+    return BINE_ERR_ARG;
+  }
+  return run_threads(comms, n, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_reduce_scatter_scaled(comms[r], algo, sbufs[r], rbufs[r], rcounts, dtype, op, scale,
+                                      comms[r]->stream);
+  });
+}
+
 int bine_loopback_run_reduce(bine_comm_t *comms, int n, int algo, const void *const *sbufs, void *const *rbufs,
                              size_t count, int dtype, int op, int root, int *statuses) {
   return run_threads(comms, n, statuses, [&](int r) {
@@ -2403,6 +2527,7 @@ int64_t bine_plan_schedule(int algo, int nranks, int rank, size_t count, const i
   a.flat_ag = (mode & 2) != 0;
   a.flat_rs = (mode & 4) != 0;
   a.flat_ag_chunked = (mode & 8) != 0;
+  a.scaled = (mode & 16) != 0;
   Plan p;
   Schedule sc;
   build(a, chunk_elems(chunk_bytes, esz), relay_min_bytes, (mode & 1) != 0, p, sc);

@@ -697,6 +697,79 @@ __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(0)" ::
 // every element sees the reference's association and operand order.  Received
 // leaves are read once: non-temporal loads.
 
+// ----------------------------------------------------------------------------
+// S(x), the scaled collectives' one multiplication (bine_amd.h): float and
+// double multiply in their own format by (float)scale resp. scale; the 16-bit
+// types are widened exactly to binary32, multiplied there by (float)scale and
+// rounded to nearest even into the 16-bit format -- two roundings, by
+// definition.  mul_of<T> is the multiplier's type (converted on the host).
+template <typename T>
+using mul_of = std::conditional_t<std::is_same_v<T, double>, double, float>;
+template <typename T>
+constexpr bool kScaleT =
+    std::is_same_v<T, float> || std::is_same_v<T, double> || std::is_same_v<T, F16> || std::is_same_v<T, BF16>;
+
+template <typename T>
+__device__ __forceinline__ T scale1(T x, mul_of<T> m) {
+  if constexpr (std::is_same_v<T, F16> || std::is_same_v<T, BF16>) {
+    // The binary32 product must exist as such before it is converted: left to
+    // itself the compiler folds widen + multiply + convert into one
+    // v_fma_mixlo_f16 (m * x + 0), and the +0 addend turns a product of -0
+    // into +0 (measured on the special-value grid: -0 * 0 gave +0).  The empty
+    // asm pins the product in a VGPR (no instruction is emitted), so the
+    // sequence is v_cvt_f32_f16, v_mul_f32, v_cvt_f16_f32.
+    float p = (float)x * m;
+    asm volatile("" : "+v"(p));
+    return (T)p;
+  } else return x * m;
+}
+// one 16-B vector.  binary16: v_cvt_f32_f16 up, packed fp32 multiply,
+// v_cvt_f16_f32 (round to nearest even -- never the packed round-toward-zero
+// conversion) down; bfloat16: widened by shift / mask as in apply16, packed
+// fp32 multiply, the hardware's nearest-even v_cvt_pk_bf16_f32 down.
+template <typename T>
+__device__ __forceinline__ u32x4_t scale16(u32x4_t v, mul_of<T> m) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  if constexpr (std::is_same_v<T, F16>) {
+    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+    typedef float f32x8 __attribute__((ext_vector_type(8)));
+    f16x8 h;
+    __builtin_memcpy(&h, &v, 16);
+    h = __builtin_convertvector(__builtin_convertvector(h, f32x8) * m, f16x8);
+    u32x4_t r;
+    __builtin_memcpy(&r, &h, 16);
+    return r;
+  } else if constexpr (std::is_same_v<T, BF16>) {
+    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+    const u32x4_t vlo = v << 16, vhi = v & 0xffff0000u;
+    f32x4 lo, hi;
+    __builtin_memcpy(&lo, &vlo, 16);
+    __builtin_memcpy(&hi, &vhi, 16);
+    lo = lo * m;
+    hi = hi * m;
+    const bf16x8 h = __builtin_convertvector(__builtin_shufflevector(lo, hi, 0, 4, 1, 5, 2, 6, 3, 7), bf16x8);
+    u32x4_t r;
+    __builtin_memcpy(&r, &h, 16);
+    return r;
+  } else if constexpr (std::is_same_v<T, double>) {
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    f64x2 d;
+    __builtin_memcpy(&d, &v, 16);
+    d = d * m;
+    u32x4_t r;
+    __builtin_memcpy(&r, &d, 16);
+    return r;
+  } else {
+    static_assert(std::is_same_v<T, float>, "scaled types: float, double, float16, bfloat16");
+    f32x4 f;
+    __builtin_memcpy(&f, &v, 16);
+    f = f * m;
+    u32x4_t r;
+    __builtin_memcpy(&r, &f, 16);
+    return r;
+  }
+}
+
 struct TreeArgs {
   const void *leaf[kMaxLeaves];
   void *out;
@@ -733,9 +806,13 @@ __device__ __forceinline__ T tree_scalar(const TreeArgs &t, size_t i) {
 // grid-stride loop, unguarded loads in every full tile (measured on MI355X,
 // tools/tree_variants.hip: a grid-strided form with a guard on every load ran
 // 31 us vs 24.5 us for 8 x 16 MiB).
-template <typename T, int OP, int NL, int U, bool GUARD>
+// SC (the scaled tree, bine_reduce_tree_scaled): the final value of every
+// vector is multiplied by `m` in registers right before its store (scale16
+// below) -- a separate instantiation; with SC = false the body is the one the
+// unscaled kernels and the direct transport's k_dm_move_tree always had.
+template <typename T, int OP, int NL, int U, bool GUARD, bool SC = false>
 __device__ __forceinline__ void tree_tile(const u32x4 *const *lp, u32x4 *vo, size_t base, size_t nvec,
-                                          unsigned swap) {
+                                          unsigned swap, mul_of<T> m = {}) {
   constexpr int G = NL < 8 ? NL : 8, NG = NL / G, LG = G == 2 ? 1 : G == 4 ? 2 : 3;
   u32x4 part[U][NG];
 #pragma unroll
@@ -774,6 +851,7 @@ __device__ __forceinline__ void tree_tile(const u32x4 *const *lp, u32x4 *vo, siz
     for (int w = 1; w < NG; w <<= 1, lvl++)
 #pragma unroll
       for (int g = 0; g < NG; g += 2 * w) part[u][g] = comb16<T, OP>(part[u][g], part[u][g + w], (swap >> lvl) & 1);
+    if constexpr (SC) part[u][0] = scale16<T>(part[u][0], m);
     const size_t i = base + (size_t)u * kBlock;
     // non-temporal stores: 23.91 vs 24.12 us at the C3 chunk shape, 0.99 of
     // the 9 streams' read-only ceiling (profiles/r3_tree_variants.txt); nt
@@ -815,9 +893,68 @@ __global__ __launch_bounds__(kBlock) void k_reduce_tree_scalar(TreeArgs t) {
     out[i] = tree_scalar<T, OP, NL>(t, i);
 }
 
+#if BINE_OPSET != 1
+// The scaled tree (bine_reduce_tree_scaled; the flagged trees of the scaled
+// collectives): sibling kernels of the three above with S applied to the final
+// value in registers -- the same loads, the same tree, the same store, one
+// multiply more per element.  Siblings, not a flag on the kernels above, so
+// that those keep their arguments and their device code.
 template <typename T, int OP, int NL>
-static hipError_t tree_nl(TreeArgs &t, hipStream_t st) {
+__global__ __launch_bounds__(kBlock) void k_reduce_tree_edges_sc(TreeArgs t, mul_of<T> m) {
+  constexpr size_t V = 16 / sizeof(T);
+  T *out = (T *)t.out;
+  for (size_t i = threadIdx.x; i < t.head; i += kBlock) out[i] = scale1<T>(tree_scalar<T, OP, NL>(t, i), m);
+  for (size_t i = t.head + t.nvec * V + threadIdx.x; i < t.n; i += kBlock)
+    out[i] = scale1<T>(tree_scalar<T, OP, NL>(t, i), m);
+}
+
+template <typename T, int OP, int NL, int U>
+__global__ __launch_bounds__(kBlock) void k_reduce_tree_sc(TreeArgs t, mul_of<T> m) {
+  T *out = (T *)t.out;
+  const u32x4 *lp[NL];
+#pragma unroll
+  for (int j = 0; j < NL; j++) lp[j] = reinterpret_cast<const u32x4 *>((const T *)t.leaf[j] + t.head);
+  u32x4 *vo = reinterpret_cast<u32x4 *>(out + t.head);
+  const size_t base = (size_t)blockIdx.x * kBlock * U + threadIdx.x;
+  if ((size_t)(blockIdx.x + 1) * kBlock * U <= t.nvec)
+    tree_tile<T, OP, NL, U, false, true>(lp, vo, base, t.nvec, t.swap, m);
+  else tree_tile<T, OP, NL, U, true, true>(lp, vo, base, t.nvec, t.swap, m);
+}
+
+template <typename T, int OP, int NL>
+__global__ __launch_bounds__(kBlock) void k_reduce_tree_scalar_sc(TreeArgs t, mul_of<T> m) {
+  T *out = (T *)t.out;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < t.n; i += (size_t)gridDim.x * kBlock)
+    out[i] = scale1<T>(tree_scalar<T, OP, NL>(t, i), m);
+}
+#endif
+
+// sc != nullptr: the scaled siblings with multiplier *sc (the four floating
+// types only; hipErrorInvalidValue for any other)
+template <typename T, int OP, int NL>
+static hipError_t tree_nl(TreeArgs &t, hipStream_t st, const double *sc) {
   constexpr int U = NL == 2 ? 8 : NL <= 8 ? 4 : 2;  // tools/tree_variants.hip: <8,4> 25.2 us, <8,2> 26.5 us
+  if (sc) {
+#if BINE_OPSET != 1
+    if constexpr (kScaleT<T>) {
+      const mul_of<T> m = (mul_of<T>)*sc;
+      if (t.vec) {
+        constexpr size_t V = 16 / sizeof(T);
+        const size_t tiles = (t.nvec + (size_t)kBlock * U - 1) / ((size_t)kBlock * U);
+        if (tiles)
+          hipLaunchKernelGGL((k_reduce_tree_sc<T, OP, NL, U>), dim3((unsigned)tiles), dim3(kBlock), 0, st, t, m);
+        if (t.head || t.head + t.nvec * V < t.n)
+          hipLaunchKernelGGL((k_reduce_tree_edges_sc<T, OP, NL>), dim3(1), dim3(kBlock), 0, st, t, m);
+      } else {
+        size_t blocks = (t.n + kBlock * 4 - 1) / (kBlock * 4);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL((k_reduce_tree_scalar_sc<T, OP, NL>), dim3((unsigned)blocks), dim3(kBlock), 0, st, t, m);
+      }
+      return hipGetLastError();
+    }
+#endif
+    return hipErrorInvalidValue;
+  }
   if (t.vec) {
     constexpr size_t V = 16 / sizeof(T);
     const size_t tiles = (t.nvec + (size_t)kBlock * U - 1) / ((size_t)kBlock * U);
@@ -833,18 +970,18 @@ static hipError_t tree_nl(TreeArgs &t, hipStream_t st) {
 }
 
 template <typename T, int OP>
-static hipError_t tree_t(int nl, TreeArgs &t, hipStream_t st) {
+static hipError_t tree_t(int nl, TreeArgs &t, hipStream_t st, const double *sc) {
   switch (nl) {
-    case 2: return tree_nl<T, OP, 2>(t, st);
-    case 4: return tree_nl<T, OP, 4>(t, st);
-    case 8: return tree_nl<T, OP, 8>(t, st);
-    case 16: return tree_nl<T, OP, 16>(t, st);
+    case 2: return tree_nl<T, OP, 2>(t, st, sc);
+    case 4: return tree_nl<T, OP, 4>(t, st, sc);
+    case 8: return tree_nl<T, OP, 8>(t, st, sc);
+    case 16: return tree_nl<T, OP, 16>(t, st, sc);
     default: return hipErrorInvalidValue;
   }
 }
 
 template <typename T>
-static hipError_t tree_op(int nl, TreeArgs &t, int op, hipStream_t st) {
+static hipError_t tree_op(int nl, TreeArgs &t, int op, hipStream_t st, const double *sc = nullptr) {
   constexpr size_t V = 16 / sizeof(T);
   const uintptr_t oo = (uintptr_t)t.out;
   bool co = (oo % sizeof(T)) == 0;
@@ -852,10 +989,13 @@ static hipError_t tree_op(int nl, TreeArgs &t, int op, hipStream_t st) {
   t.vec = co ? 1 : 0;
   t.head = co ? std::min<uint64_t>(((16 - (oo & 15)) & 15) / sizeof(T), t.n) : t.n;
   t.nvec = co ? (t.n - t.head) / V : 0;
-#define CALL(OP) tree_t<T, OP>(nl, t, st)
+#define CALL(OP) tree_t<T, OP>(nl, t, st, sc)
   BINE_OP_SWITCH(T, CALL)
 #undef CALL
 }
+
+static int reduce_tree_run(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op, void *stream,
+                           unsigned swap, const double *sc);
 
 int BINE_FN(launch_reduce_tree)(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
                                 void *stream, unsigned swap) {
@@ -864,6 +1004,25 @@ int BINE_FN(launch_reduce_tree)(int nl, const void *const *leaf, void *out, size
   if (h16_dtype(dtype)) return launch_reduce_tree_h16(nl, leaf, out, count, dtype, op, stream, swap);
   if (ext_op(dtype, op)) return launch_reduce_tree_logic(nl, leaf, out, count, dtype, op, stream, swap);
 #endif
+  return reduce_tree_run(nl, leaf, out, count, dtype, op, stream, swap, nullptr);
+}
+
+#if BINE_OPSET != 1
+// the same tree with S applied to every final value in the same launch
+// (k_reduce_tree_sc); the caller has checked bine_scale_valid(dtype, op)
+int BINE_FN(launch_reduce_tree_scaled)(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
+                                       void *stream, unsigned swap, double scale) {
+  if (!bine_scale_valid(dtype, op)) return BINE_ERR_ARG;
+  if (count == 0) return BINE_SUCCESS;
+#if BINE_OPSET == 0
+  if (h16_dtype(dtype)) return launch_reduce_tree_scaled_h16(nl, leaf, out, count, dtype, op, stream, swap, scale);
+#endif
+  return reduce_tree_run(nl, leaf, out, count, dtype, op, stream, swap, &scale);
+}
+#endif
+
+static int reduce_tree_run(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op, void *stream,
+                           unsigned swap, const double *sc) {
   if (nl < 2 || nl > kMaxLeaves || (nl & (nl - 1))) return BINE_ERR_ARG;
   size_t scale;
   dtype = canon_dtype(dtype, op, &scale);
@@ -877,33 +1036,122 @@ int BINE_FN(launch_reduce_tree)(int nl, const void *const *leaf, void *out, size
   hipError_t e;
   switch (dtype) {
 #if BINE_OPSET == 2
-    case BINE_FLOAT16: e = tree_op<F16>(nl, t, op, st); break;
-    case BINE_BFLOAT16: e = tree_op<BF16>(nl, t, op, st); break;
+    case BINE_FLOAT16: e = tree_op<F16>(nl, t, op, st, sc); break;
+    case BINE_BFLOAT16: e = tree_op<BF16>(nl, t, op, st, sc); break;
 #else
-    case BINE_INT8: e = tree_op<int8_t>(nl, t, op, st); break;
-    case BINE_UINT8: e = tree_op<uint8_t>(nl, t, op, st); break;
-    case BINE_INT16: e = tree_op<int16_t>(nl, t, op, st); break;
-    case BINE_UINT16: e = tree_op<uint16_t>(nl, t, op, st); break;
-    case BINE_INT32: e = tree_op<int32_t>(nl, t, op, st); break;
-    case BINE_UINT32: e = tree_op<uint32_t>(nl, t, op, st); break;
-    case BINE_INT64: e = tree_op<int64_t>(nl, t, op, st); break;
-    case BINE_UINT64: e = tree_op<uint64_t>(nl, t, op, st); break;
-    case BINE_FLOAT: e = tree_op<float>(nl, t, op, st); break;
-    case BINE_DOUBLE: e = tree_op<double>(nl, t, op, st); break;
+    case BINE_INT8: e = tree_op<int8_t>(nl, t, op, st, sc); break;
+    case BINE_UINT8: e = tree_op<uint8_t>(nl, t, op, st, sc); break;
+    case BINE_INT16: e = tree_op<int16_t>(nl, t, op, st, sc); break;
+    case BINE_UINT16: e = tree_op<uint16_t>(nl, t, op, st, sc); break;
+    case BINE_INT32: e = tree_op<int32_t>(nl, t, op, st, sc); break;
+    case BINE_UINT32: e = tree_op<uint32_t>(nl, t, op, st, sc); break;
+    case BINE_INT64: e = tree_op<int64_t>(nl, t, op, st, sc); break;
+    case BINE_UINT64: e = tree_op<uint64_t>(nl, t, op, st, sc); break;
+    case BINE_FLOAT: e = tree_op<float>(nl, t, op, st, sc); break;
+    case BINE_DOUBLE: e = tree_op<double>(nl, t, op, st, sc); break;
 #endif
 #if BINE_OPSET == 1
-    case BINE_FLOAT_INT: e = tree_op<Pair<float>>(nl, t, op, st); break;
-    case BINE_DOUBLE_INT: e = tree_op<Pair<double>>(nl, t, op, st); break;
-    case BINE_LONG_INT: e = tree_op<Pair<long>>(nl, t, op, st); break;
-    case BINE_2INT: e = tree_op<Pair<int>>(nl, t, op, st); break;
-    case BINE_SHORT_INT: e = tree_op<Pair<short>>(nl, t, op, st); break;
-    case BINE_C_FLOAT_COMPLEX: e = tree_op<Cplx<float>>(nl, t, op, st); break;
-    case BINE_C_DOUBLE_COMPLEX: e = tree_op<Cplx<double>>(nl, t, op, st); break;
+    case BINE_FLOAT_INT: e = tree_op<Pair<float>>(nl, t, op, st, sc); break;
+    case BINE_DOUBLE_INT: e = tree_op<Pair<double>>(nl, t, op, st, sc); break;
+    case BINE_LONG_INT: e = tree_op<Pair<long>>(nl, t, op, st, sc); break;
+    case BINE_2INT: e = tree_op<Pair<int>>(nl, t, op, st, sc); break;
+    case BINE_SHORT_INT: e = tree_op<Pair<short>>(nl, t, op, st, sc); break;
+    case BINE_C_FLOAT_COMPLEX: e = tree_op<Cplx<float>>(nl, t, op, st, sc); break;
+    case BINE_C_DOUBLE_COMPLEX: e = tree_op<Cplx<double>>(nl, t, op, st, sc); break;
 #endif
     default: return BINE_ERR_UNSUPPORTED;
   }
   return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
 }
+
+#if BINE_OPSET != 1
+// ----------------------------------------------------------------------------
+// k_scale: out[i] = S(in[i]) (bine_scale; the trailing SCALE primitive of the
+// scaled collectives).  k_copy's shape: one tile of kBlock * kScaleU 16-B
+// vectors per workgroup, every load issued before the first store,
+// non-temporal stores; the loads non-temporal too when out of place (OOP: the
+// input is read once), plain in place (the line is written right back).
+// Elements before the first 16-B boundary of `out` and after the last full
+// vector go scalar through workgroup 0; operands that are not co-aligned mod
+// 16 B take the scalar grid-stride kernel.  `in` may equal `out`.
+constexpr int kScaleU = 8;
+
+template <typename T, bool OOP>
+__global__ __launch_bounds__(kBlock) void k_scale(const T *in, T *out, size_t head, size_t nvec, size_t n,
+                                                  mul_of<T> m) {
+  constexpr size_t V = 16 / sizeof(T);
+  if (blockIdx.x == 0) {
+    for (size_t i = threadIdx.x; i < head; i += kBlock) out[i] = scale1<T>(in[i], m);
+    for (size_t i = head + nvec * V + threadIdx.x; i < n; i += kBlock) out[i] = scale1<T>(in[i], m);
+  }
+  const u32x4 *vs = reinterpret_cast<const u32x4 *>(in + head);
+  u32x4 *vd = reinterpret_cast<u32x4 *>(out + head);
+  const size_t base = (size_t)blockIdx.x * kBlock * kScaleU + threadIdx.x;
+  if (base + (kScaleU - 1) * (size_t)kBlock < nvec) {
+    u32x4 x[kScaleU];
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) x[u] = ld<OOP>(vs + base + (size_t)u * kBlock);
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++)
+      __builtin_nontemporal_store(scale16<T>(x[u], m), vd + base + (size_t)u * kBlock);
+  } else {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if (i < nvec) vd[i] = scale16<T>(vs[i], m);
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_scale_scalar(const T *in, T *out, size_t n, mul_of<T> m) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
+    out[i] = scale1<T>(in[i], m);
+}
+
+template <typename T>
+static hipError_t scale_t(const void *in, void *out, size_t n, double scale, hipStream_t st) {
+  constexpr size_t V = 16 / sizeof(T);
+  const mul_of<T> m = (mul_of<T>)scale;  // (float)scale: round to nearest even
+  const T *pi = (const T *)in;
+  T *po = (T *)out;
+  const uintptr_t io = (uintptr_t)in, oo = (uintptr_t)out;
+  if (((io ^ oo) & 15) != 0 || (oo % sizeof(T)) != 0) {
+    size_t blocks = (n + kBlock * 4 - 1) / (kBlock * 4);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL((k_scale_scalar<T>), dim3((unsigned)blocks), dim3(kBlock), 0, st, pi, po, n, m);
+    return hipGetLastError();
+  }
+  const size_t head = std::min<size_t>(((16 - (oo & 15)) & 15) / sizeof(T), n);
+  const size_t nvec = (n - head) / V;
+  const size_t tiles = (nvec + (size_t)kBlock * kScaleU - 1) / ((size_t)kBlock * kScaleU);
+  const unsigned blocks = (unsigned)(tiles ? tiles : 1);
+  if (in == out) hipLaunchKernelGGL((k_scale<T, false>), dim3(blocks), dim3(kBlock), 0, st, pi, po, head, nvec, n, m);
+  else hipLaunchKernelGGL((k_scale<T, true>), dim3(blocks), dim3(kBlock), 0, st, pi, po, head, nvec, n, m);
+  return hipGetLastError();
+}
+
+int BINE_FN(launch_scale)(const void *in, void *out, size_t count, int dtype, double scale, void *stream) {
+  if (!bine_scale_valid(dtype, BINE_SUM)) return BINE_ERR_ARG;
+  if (count == 0) return BINE_SUCCESS;
+#if BINE_OPSET == 0
+  if (h16_dtype(dtype)) return launch_scale_h16(in, out, count, dtype, scale, stream);
+#endif
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e;
+  switch (dtype) {
+#if BINE_OPSET == 2
+    case BINE_FLOAT16: e = scale_t<F16>(in, out, count, scale, st); break;
+    case BINE_BFLOAT16: e = scale_t<BF16>(in, out, count, scale, st); break;
+#else
+    case BINE_FLOAT: e = scale_t<float>(in, out, count, scale, st); break;
+    case BINE_DOUBLE: e = scale_t<double>(in, out, count, scale, st); break;
+#endif
+    default: return BINE_ERR_ARG;
+  }
+  return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+}
+#endif  // BINE_OPSET != 1
 
 #if BINE_OPSET == 0
 // ----------------------------------------------------------------------------

@@ -310,7 +310,12 @@ bool flat_rs(Builder &b, const PlanArgs &a, int src, const std::vector<uint64_t>
     b.end();
     if (agc && k > 0) flat_ag_chunk(b, a, boff, bcnt, o - ch, ch);
     b.reduce_tree(P, pos, src, boff[(size_t)r] + o, T0, base, out, out_off + o, cl, swap);
+    // scaled call: this tree's output is a final value of the collective (every
+    // allreduce / reduce-scatter caller of flat_rs only moves it afterwards),
+    // so the tree scales it; make_plan then appends no trailing SCALE
+    if (a.scaled && cl) b.p.prims.back().flags |= BINE_PRIM_SCALED;
   }
+  if (a.scaled) b.p.scale_fused = true;
   if (agc && k > 0) flat_ag_chunk(b, a, boff, bcnt, (k - 1) * ch, ch);
   return agc;
 }
@@ -2194,7 +2199,37 @@ void rooted_flat(Builder &b, const PlanArgs &a) {
   b.end();
 }
 
+// scaled call without scaling trees: one in-place SCALE of this rank's output,
+// after everything else
+void append_scale(Plan &p, const PlanArgs &a) {
+  if (p.status != BINE_SUCCESS || p.scale_fused) return;
+  const bool rs = a.algo >= BINE_RS_RECURSIVEHALVING && a.algo <= BINE_RS_BINE_BLOCK_BY_BLOCK_ANY_EVEN;
+  const uint64_t n = rs ? (uint64_t)a.rcounts[(size_t)a.rank] : (uint64_t)a.count;
+  if (n == 0) return;
+  Prim x = Builder::mk(BINE_PRIM_SCALE);
+  x.src_buf = x.dst_buf = RB;
+  x.count = n;
+  p.prims.push_back(x);
+}
+
+static Plan make_plan_unscaled(const PlanArgs &a);
+
 Plan make_plan(const PlanArgs &a) {
+  const bool ar = a.algo >= BINE_AR_RECURSIVEDOUBLING && a.algo <= BINE_AR_BINE_BLOCK_BY_BLOCK_ANY_EVEN;
+  const bool rs = a.algo >= BINE_RS_RECURSIVEHALVING && a.algo <= BINE_RS_BINE_BLOCK_BY_BLOCK_ANY_EVEN;
+  if (a.scaled && !ar && !rs) {
+    Plan p;
+    p.status = BINE_ERR_UNSUPPORTED;
+    return p;
+  }
+  Plan p = make_plan_unscaled(a);
+  if (a.scaled) append_scale(p, a);
+  return p;
+}
+
+// (with a.scaled: the flat reduce-scatter's trees flagged, Plan::scale_fused
+// set where they are; the trailing SCALE is make_plan's)
+static Plan make_plan_unscaled(const PlanArgs &a) {
   Builder b(a.rank);
   if (a.P < 1 || a.rank < 0 || a.rank >= a.P || a.esz == 0) { b.fail(BINE_ERR_ARG); return b.p; }
   const bool rs = a.algo >= BINE_RS_RECURSIVEHALVING && a.algo <= BINE_RS_BINE_BLOCK_BY_BLOCK_ANY_EVEN;

@@ -123,6 +123,7 @@ Plan make_tree_plan(const PlanArgs &a) {
     PlanArgs b = a;
     b.flat_ag = false;  // instances keep their own (mirrored) allgather
     b.flat_rs = false;  // and their own halving steps
+    b.scaled = false;   // a scaled call: one trailing SCALE over the whole output, below
     b.rank = v;
     Mapper m;
     if (allreduce) {
@@ -189,6 +190,7 @@ Plan make_tree_plan(const PlanArgs &a) {
         }
     if (any) gid++;
   }
+  if (a.scaled) append_scale(out, a);
   return out;
 }
 
