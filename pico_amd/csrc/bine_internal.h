@@ -152,15 +152,18 @@ int launch_reduce_batch(int n, const void *const *a, const void *const *b, void 
 constexpr int kMaxLeaves = 16;
 int launch_reduce_tree(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op, void *stream,
                        unsigned swap = 0);
-// the logical / bitwise ops' instantiations (kernels.hip compiled with
-// BINE_OPSET=1); the entry points above forward those ops here
+// kernels.hip is compiled three times; the entry points above live in the
+// BINE_OPSET=0 object and forward a (dtype, op) another object holds
+// (kernels.hip owner_opset) to that object's twin below.  Each object picks
+// its instantiation through the same with_dtype / with_op / with_nl
+// dispatchers; a dtype an object does not hold is BINE_ERR_UNSUPPORTED there.
+// BINE_OPSET=1: the logical / bitwise / loc ops and the pair and complex types
 int launch_reduce_logic(const void *a, const void *b, void *out, size_t count, int dtype, int op, void *stream);
 int launch_reduce_batch_logic(int n, const void *const *a, const void *const *b, void *const *out,
                               const size_t *count, int dtype, int op, void *stream);
 int launch_reduce_tree_logic(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
                              void *stream, unsigned swap);
-// the 16-bit floating types' instantiations (kernels.hip compiled with
-// BINE_OPSET=2); the entry points above forward BINE_FLOAT16 / BINE_BFLOAT16 here
+// BINE_OPSET=2: BINE_FLOAT16 / BINE_BFLOAT16
 int launch_reduce_h16(const void *a, const void *b, void *out, size_t count, int dtype, int op, void *stream);
 int launch_reduce_batch_h16(int n, const void *const *a, const void *const *b, void *const *out,
                             const size_t *count, int dtype, int op, void *stream);

@@ -41,6 +41,14 @@
 // points); BINE_OPSET 2 -> kernels_h16.o, the reduction kernels'
 // instantiations for the 16-bit floating types (launch_*_h16, reached the
 // same way).  Three translation units compile in parallel.
+//
+// Adding an element type: (1) a case in with_dtype, under the BINE_OPSET of
+// the compilation that is to hold it -- every reduce-family entry point, the
+// fill and the scale dispatch through that one list (with_op says which ops a
+// type gets; kScaleT / kDmT whether the scaled kernels / the direct
+// transport's in-launch reductions take it); (2) if another compilation than
+// opset 0 holds it, owner_opset, so that the opset-0 entry points forward it.
+// Outside this file: bine_op_valid / bine_dtype_size (executor.cpp).
 #ifndef BINE_OPSET
 #define BINE_OPSET 0
 #endif
@@ -192,44 +200,107 @@ constexpr bool kPairT = is_pair<T>::value;
 template <typename T>
 constexpr bool kCplxT = is_cplx<T>::value;
 
-// BINE_OP_SWITCH(T, CALL): `return CALL(OP)` for the op in variable `op`,
-// only for the (T, OP) pairs instantiated; hipErrorInvalidValue otherwise
-#if BINE_OPSET != 1
-#define BINE_OP_SWITCH(T, CALL)                                      \
-  switch (op) {                                                      \
-    case BINE_SUM: return CALL(BINE_SUM);                            \
-    case BINE_PROD: return CALL(BINE_PROD);                          \
-    case BINE_MAX: return CALL(BINE_MAX);                            \
-    case BINE_MIN: return CALL(BINE_MIN);                            \
-    default: break;                                                  \
-  }                                                                  \
-  return hipErrorInvalidValue;
-#else
-#define BINE_OP_SWITCH(T, CALL)                                      \
-  switch (op) {                                                      \
-    case BINE_SUM: if constexpr (kCplxT<T>) return CALL(BINE_SUM); break;   \
-    case BINE_PROD: if constexpr (kCplxT<T>) return CALL(BINE_PROD); break; \
-    case BINE_LAND: if constexpr (kLogicT<T>) return CALL(BINE_LAND); break; \
-    case BINE_LOR: if constexpr (kLogicT<T>) return CALL(BINE_LOR); break;   \
-    case BINE_LXOR: if constexpr (kLogicT<T>) return CALL(BINE_LXOR); break; \
-    case BINE_BAND: if constexpr (kBitsT<T>) return CALL(BINE_BAND); break;  \
-    case BINE_BOR: if constexpr (kBitsT<T>) return CALL(BINE_BOR); break;    \
-    case BINE_BXOR: if constexpr (kBitsT<T>) return CALL(BINE_BXOR); break;  \
-    case BINE_MAXLOC: if constexpr (kPairT<T>) return CALL(BINE_MAXLOC); break; \
-    case BINE_MINLOC: if constexpr (kPairT<T>) return CALL(BINE_MINLOC); break; \
-    default: break;                                                  \
-  }                                                                  \
-  return hipErrorInvalidValue;
-#endif
+// ---- host dispatch: run-time (dtype, op, nl) -> template arguments ---------
+// Each dispatcher calls a generic lambda with a tag whose type carries the
+// compile-time value, only for the values this compilation instantiates.
 
+template <typename T, int DT>
+struct dtype_tag {
+  using type = T;
+  static constexpr int id = DT;
+};
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+static int status(hipError_t e) { return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP; }
+
+// with_dtype(dtype, f): f(dtype_tag<T, dtype>{}), a BINE_* status, for the
+// element type T of `dtype`; BINE_ERR_UNSUPPORTED for a dtype this
+// compilation does not hold
+template <typename F>
+static int with_dtype(int dtype, F &&f) {
+  switch (dtype) {
+#if BINE_OPSET == 2
+    case BINE_FLOAT16: return f(dtype_tag<F16, BINE_FLOAT16>{});
+    case BINE_BFLOAT16: return f(dtype_tag<BF16, BINE_BFLOAT16>{});
+#else
+    case BINE_INT8: return f(dtype_tag<int8_t, BINE_INT8>{});
+    case BINE_UINT8: return f(dtype_tag<uint8_t, BINE_UINT8>{});
+    case BINE_INT16: return f(dtype_tag<int16_t, BINE_INT16>{});
+    case BINE_UINT16: return f(dtype_tag<uint16_t, BINE_UINT16>{});
+    case BINE_INT32: return f(dtype_tag<int32_t, BINE_INT32>{});
+    case BINE_UINT32: return f(dtype_tag<uint32_t, BINE_UINT32>{});
+    case BINE_INT64: return f(dtype_tag<int64_t, BINE_INT64>{});
+    case BINE_UINT64: return f(dtype_tag<uint64_t, BINE_UINT64>{});
+    case BINE_FLOAT: return f(dtype_tag<float, BINE_FLOAT>{});
+    case BINE_DOUBLE: return f(dtype_tag<double, BINE_DOUBLE>{});
+#endif
+#if BINE_OPSET == 1
+    case BINE_FLOAT_INT: return f(dtype_tag<Pair<float>, BINE_FLOAT_INT>{});
+    case BINE_DOUBLE_INT: return f(dtype_tag<Pair<double>, BINE_DOUBLE_INT>{});
+    case BINE_LONG_INT: return f(dtype_tag<Pair<long>, BINE_LONG_INT>{});
+    case BINE_2INT: return f(dtype_tag<Pair<int>, BINE_2INT>{});
+    case BINE_SHORT_INT: return f(dtype_tag<Pair<short>, BINE_SHORT_INT>{});
+    case BINE_C_FLOAT_COMPLEX: return f(dtype_tag<Cplx<float>, BINE_C_FLOAT_COMPLEX>{});
+    case BINE_C_DOUBLE_COMPLEX: return f(dtype_tag<Cplx<double>, BINE_C_DOUBLE_COMPLEX>{});
+#endif
+    default: return BINE_ERR_UNSUPPORTED;
+  }
+}
+
+// with_op<T>(op, f, none): f(int_c<OP>{}) for the (T, OP) pairs this
+// compilation instantiates; `none` for every other op
+template <typename T, typename F, typename R = hipError_t>
+static R with_op(int op, F &&f, R none = hipErrorInvalidValue) {
+  switch (op) {
+#if BINE_OPSET != 1
+    case BINE_SUM: return f(int_c<BINE_SUM>{});
+    case BINE_PROD: return f(int_c<BINE_PROD>{});
+    case BINE_MAX: return f(int_c<BINE_MAX>{});
+    case BINE_MIN: return f(int_c<BINE_MIN>{});
+#else
+    case BINE_SUM: if constexpr (kCplxT<T>) return f(int_c<BINE_SUM>{}); break;
+    case BINE_PROD: if constexpr (kCplxT<T>) return f(int_c<BINE_PROD>{}); break;
+    case BINE_LAND: if constexpr (kLogicT<T>) return f(int_c<BINE_LAND>{}); break;
+    case BINE_LOR: if constexpr (kLogicT<T>) return f(int_c<BINE_LOR>{}); break;
+    case BINE_LXOR: if constexpr (kLogicT<T>) return f(int_c<BINE_LXOR>{}); break;
+    case BINE_BAND: if constexpr (kBitsT<T>) return f(int_c<BINE_BAND>{}); break;
+    case BINE_BOR: if constexpr (kBitsT<T>) return f(int_c<BINE_BOR>{}); break;
+    case BINE_BXOR: if constexpr (kBitsT<T>) return f(int_c<BINE_BXOR>{}); break;
+    case BINE_MAXLOC: if constexpr (kPairT<T>) return f(int_c<BINE_MAXLOC>{}); break;
+    case BINE_MINLOC: if constexpr (kPairT<T>) return f(int_c<BINE_MINLOC>{}); break;
+#endif
+    default: break;
+  }
+  return none;
+}
+
+// with_nl(nl, f, none): f(int_c<NL>{}) for the leaf counts the tree kernels
+// are instantiated for
+template <typename F, typename R = hipError_t>
+static R with_nl(int nl, F &&f, R none = hipErrorInvalidValue) {
+  switch (nl) {
+    case 2: return f(int_c<2>{});
+    case 4: return f(int_c<4>{});
+    case 8: return f(int_c<8>{});
+    case 16: return f(int_c<16>{});
+    default: return none;
+  }
+}
+
+#if BINE_OPSET == 0
 // the (type, op) pairs the opset-1 compilation holds: the logical / bitwise /
 // loc ops, and the pair and complex types
-[[maybe_unused]] static bool ext_op(int dtype, int op) {
+static bool ext_op(int dtype, int op) {
   return (op >= BINE_LAND && op < BINE_NUM_OPS) || (dtype >= BINE_FLOAT_INT && dtype < BINE_NUM_DTYPES);
 }
 // the types the opset-2 compilation holds (every op: the ones not defined on
 // them are refused there, by canon_dtype)
-[[maybe_unused]] static bool h16_dtype(int dtype) { return dtype == BINE_FLOAT16 || dtype == BINE_BFLOAT16; }
+static bool h16_dtype(int dtype) { return dtype == BINE_FLOAT16 || dtype == BINE_BFLOAT16; }
+// the BINE_OPSET of the compilation that holds the kernels of (dtype, op);
+// the entry points below forward to launch_*_h16 (2) / launch_*_logic (1)
+static int owner_opset(int dtype, int op) { return h16_dtype(dtype) ? 2 : ext_op(dtype, op) ? 1 : 0; }
+#endif
 
 // the element type an op runs on (see kLogicT / kBitsT); *scale = elements
 // of the run type per element of `dtype`; -1: the op is not defined on the
@@ -300,6 +371,23 @@ __device__ __forceinline__ u32x4_t apply16(u32x4_t vb, u32x4_t va) {
 constexpr int kBlock = 256;
 using u32x4 = u32x4_t;  // one global_load/store_dwordx4 per lane
 
+// launch geometry shared by the kernels below ----------------------------------
+// Operands co-aligned mod 16 B: `head` elements of `esz` bytes up to the
+// first 16-B boundary of `out` (at most n), then `nvec` whole 16-B vectors;
+// the rest is the scalar tail.
+struct VecSplit {
+  size_t head, nvec;
+};
+static VecSplit vec_split(uintptr_t out, size_t n, size_t esz) {
+  const size_t head = std::min<size_t>(((16 - (out & 15)) & 15) / esz, n);
+  return {head, (n - head) / (16 / esz)};
+}
+// workgroups of a scalar grid-stride kernel over n elements: four elements
+// per lane, at most 2048 workgroups
+static unsigned scalar_blocks(size_t n) {
+  return (unsigned)std::min<size_t>((n + kBlock * 4 - 1) / (kBlock * 4), 2048);
+}
+
 // Elements [0, head) and [head + 16/sizeof(T) * nvec, n) are done scalar by
 // block 0; the 16-B aligned middle is vectorized.  NT is a cache-policy mask:
 // bit 0 = non-temporal loads of `a` (the received operand, read exactly once),
@@ -368,17 +456,10 @@ static int g_unroll = 0, g_maxblocks = 0, g_nt = kDefaultNT;
 
 template <typename T, int OP, int U, int NT>
 static hipError_t run_reduce(const T *a, const T *b, T *out, size_t n, hipStream_t st) {
-  constexpr size_t V = 16 / sizeof(T);
   const uintptr_t ao = (uintptr_t)a, bo = (uintptr_t)b, oo = (uintptr_t)out;
-  size_t head, nvec;
-  if (((ao ^ oo) & 15) == 0 && ((bo ^ oo) & 15) == 0 && (oo % sizeof(T)) == 0) {
-    head = ((16 - (oo & 15)) & 15) / sizeof(T);
-    if (head > n) head = n;
-    nvec = (n - head) / V;
-  } else {  // operands not co-aligned mod 16 B (small runs only, see reduce_t)
-    head = n;
-    nvec = 0;
-  }
+  // operands not co-aligned mod 16 B (small runs only, see reduce_t): all scalar
+  const bool co = ((ao ^ oo) & 15) == 0 && ((bo ^ oo) & 15) == 0 && (oo % sizeof(T)) == 0;
+  const auto [head, nvec] = co ? vec_split(oo, n, sizeof(T)) : VecSplit{n, 0};
   int blocks;
   if (nvec == 0) blocks = 1;
   else {
@@ -404,9 +485,7 @@ static hipError_t reduce_t(const void *a, const void *b, void *out, size_t n, hi
   T *po = (T *)out;
   const uintptr_t ao = (uintptr_t)a, bo = (uintptr_t)b, oo = (uintptr_t)out;
   if ((((ao ^ oo) & 15) != 0 || ((bo ^ oo) & 15) != 0) && n > 4096) {
-    size_t blocks = (n + kBlock * 4 - 1) / (kBlock * 4);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL((k_reduce_scalar<T, OP>), dim3((unsigned)blocks), dim3(kBlock), 0, st, pa, pb, po, n);
+    hipLaunchKernelGGL((k_reduce_scalar<T, OP>), dim3(scalar_blocks(n)), dim3(kBlock), 0, st, pa, pb, po, n);
     return hipGetLastError();
   }
   if constexpr (std::is_same_v<T, float> && OP == BINE_SUM) {
@@ -432,18 +511,12 @@ static hipError_t reduce_t(const void *a, const void *b, void *out, size_t n, hi
   return run_reduce<T, OP, kDefaultUnroll, kDefaultNT>(pa, pb, po, n, st);
 }
 
-template <typename T>
-static hipError_t reduce_op(const void *a, const void *b, void *out, size_t n, int op, hipStream_t st) {
-#define CALL(OP) reduce_t<T, OP>(a, b, out, n, st)
-  BINE_OP_SWITCH(T, CALL)
-#undef CALL
-}
-
 int BINE_FN(launch_reduce)(const void *a, const void *b, void *out, size_t count, int dtype, int op, void *stream) {
   if (count == 0) return BINE_SUCCESS;
 #if BINE_OPSET == 0
-  if (h16_dtype(dtype)) return launch_reduce_h16(a, b, out, count, dtype, op, stream);
-  if (ext_op(dtype, op)) return launch_reduce_logic(a, b, out, count, dtype, op, stream);
+  if (const int o = owner_opset(dtype, op))
+    return o == 2 ? launch_reduce_h16(a, b, out, count, dtype, op, stream)
+                  : launch_reduce_logic(a, b, out, count, dtype, op, stream);
 #endif
   size_t scale;
   dtype = canon_dtype(dtype, op, &scale);
@@ -451,35 +524,10 @@ int BINE_FN(launch_reduce)(const void *a, const void *b, void *out, size_t count
   count *= scale;
   read_tuning();
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  switch (dtype) {
-#if BINE_OPSET == 2
-    case BINE_FLOAT16: e = reduce_op<F16>(a, b, out, count, op, st); break;
-    case BINE_BFLOAT16: e = reduce_op<BF16>(a, b, out, count, op, st); break;
-#else
-    case BINE_INT8: e = reduce_op<int8_t>(a, b, out, count, op, st); break;
-    case BINE_UINT8: e = reduce_op<uint8_t>(a, b, out, count, op, st); break;
-    case BINE_INT16: e = reduce_op<int16_t>(a, b, out, count, op, st); break;
-    case BINE_UINT16: e = reduce_op<uint16_t>(a, b, out, count, op, st); break;
-    case BINE_INT32: e = reduce_op<int32_t>(a, b, out, count, op, st); break;
-    case BINE_UINT32: e = reduce_op<uint32_t>(a, b, out, count, op, st); break;
-    case BINE_INT64: e = reduce_op<int64_t>(a, b, out, count, op, st); break;
-    case BINE_UINT64: e = reduce_op<uint64_t>(a, b, out, count, op, st); break;
-    case BINE_FLOAT: e = reduce_op<float>(a, b, out, count, op, st); break;
-    case BINE_DOUBLE: e = reduce_op<double>(a, b, out, count, op, st); break;
-#endif
-#if BINE_OPSET == 1
-    case BINE_FLOAT_INT: e = reduce_op<Pair<float>>(a, b, out, count, op, st); break;
-    case BINE_DOUBLE_INT: e = reduce_op<Pair<double>>(a, b, out, count, op, st); break;
-    case BINE_LONG_INT: e = reduce_op<Pair<long>>(a, b, out, count, op, st); break;
-    case BINE_2INT: e = reduce_op<Pair<int>>(a, b, out, count, op, st); break;
-    case BINE_SHORT_INT: e = reduce_op<Pair<short>>(a, b, out, count, op, st); break;
-    case BINE_C_FLOAT_COMPLEX: e = reduce_op<Cplx<float>>(a, b, out, count, op, st); break;
-    case BINE_C_DOUBLE_COMPLEX: e = reduce_op<Cplx<double>>(a, b, out, count, op, st); break;
-#endif
-    default: return BINE_ERR_UNSUPPORTED;
-  }
-  return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return status(with_op<T>(op, [&](auto opc) { return reduce_t<T, decltype(opc)::value>(a, b, out, count, st); }));
+  });
 }
 
 #if BINE_OPSET == 0
@@ -523,9 +571,7 @@ int launch_copy(void *dst, const void *src, size_t bytes, void *stream) {
     // 16-B aligned buffers): the runtime's device copy
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
   }
-  size_t head = (16 - (dO & 15)) & 15;
-  if (head > bytes) head = bytes;
-  const size_t nvec = (bytes - head) / 16;
+  const auto [head, nvec] = vec_split(dO, bytes, 1);
   const size_t tiles = (nvec + (size_t)kBlock * kCopyU - 1) / ((size_t)kBlock * kCopyU);
   const unsigned blocks = (unsigned)(tiles ? tiles : 1);
   hipLaunchKernelGGL(k_copy, dim3(blocks), dim3(kBlock), 0, st, (const uint8_t *)src, (uint8_t *)dst, head, nvec,
@@ -592,7 +638,6 @@ template <typename T, int OP>
 static hipError_t batch_t(int n, const void *const *a, const void *const *b, void *const *out,
                           const size_t *count, hipStream_t st) {
   constexpr int U = kDefaultUnroll;
-  constexpr size_t V = 16 / sizeof(T);
   Batch bt;
   bt.nwin = n;
   uint64_t tiles = 0;
@@ -604,8 +649,9 @@ static hipError_t batch_t(int n, const void *const *a, const void *const *b, voi
     w.b = b[k];
     w.out = out[k];
     w.n = count[k];
-    w.head = std::min<uint64_t>(((16 - (oo & 15)) & 15) / sizeof(T), w.n);
-    w.nvec = (w.n - w.head) / V;
+    const VecSplit vs = vec_split(oo, count[k], sizeof(T));
+    w.head = vs.head;
+    w.nvec = vs.nvec;
     w.tile0 = tiles;
     tiles += std::max<uint64_t>(1, (w.nvec + (uint64_t)kBlock * U - 1) / ((uint64_t)kBlock * U));
   }
@@ -613,20 +659,13 @@ static hipError_t batch_t(int n, const void *const *a, const void *const *b, voi
   return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t batch_op(int n, const void *const *a, const void *const *b, void *const *out, const size_t *c,
-                           int op, hipStream_t st) {
-#define CALL(OP) batch_t<T, OP>(n, a, b, out, c, st)
-  BINE_OP_SWITCH(T, CALL)
-#undef CALL
-}
-
 int BINE_FN(launch_reduce_batch)(int n, const void *const *a, const void *const *b, void *const *out,
                                  const size_t *count_in, int dtype, int op, void *stream) {
   if (n < 1 || n > kMaxBatch) return BINE_ERR_ARG;
 #if BINE_OPSET == 0
-  if (h16_dtype(dtype)) return launch_reduce_batch_h16(n, a, b, out, count_in, dtype, op, stream);
-  if (ext_op(dtype, op)) return launch_reduce_batch_logic(n, a, b, out, count_in, dtype, op, stream);
+  if (const int o = owner_opset(dtype, op))
+    return o == 2 ? launch_reduce_batch_h16(n, a, b, out, count_in, dtype, op, stream)
+                  : launch_reduce_batch_logic(n, a, b, out, count_in, dtype, op, stream);
 #endif
   size_t scale;
   dtype = canon_dtype(dtype, op, &scale);
@@ -634,36 +673,13 @@ int BINE_FN(launch_reduce_batch)(int n, const void *const *a, const void *const 
   size_t count[kMaxBatch];
   for (int k = 0; k < n; k++) count[k] = count_in[k] * scale;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  switch (dtype) {
-#if BINE_OPSET == 2
-    case BINE_FLOAT16: e = batch_op<F16>(n, a, b, out, count, op, st); break;
-    case BINE_BFLOAT16: e = batch_op<BF16>(n, a, b, out, count, op, st); break;
-#else
-    case BINE_INT8: e = batch_op<int8_t>(n, a, b, out, count, op, st); break;
-    case BINE_UINT8: e = batch_op<uint8_t>(n, a, b, out, count, op, st); break;
-    case BINE_INT16: e = batch_op<int16_t>(n, a, b, out, count, op, st); break;
-    case BINE_UINT16: e = batch_op<uint16_t>(n, a, b, out, count, op, st); break;
-    case BINE_INT32: e = batch_op<int32_t>(n, a, b, out, count, op, st); break;
-    case BINE_UINT32: e = batch_op<uint32_t>(n, a, b, out, count, op, st); break;
-    case BINE_INT64: e = batch_op<int64_t>(n, a, b, out, count, op, st); break;
-    case BINE_UINT64: e = batch_op<uint64_t>(n, a, b, out, count, op, st); break;
-    case BINE_FLOAT: e = batch_op<float>(n, a, b, out, count, op, st); break;
-    case BINE_DOUBLE: e = batch_op<double>(n, a, b, out, count, op, st); break;
-#endif
-#if BINE_OPSET == 1
-    case BINE_FLOAT_INT: e = batch_op<Pair<float>>(n, a, b, out, count, op, st); break;
-    case BINE_DOUBLE_INT: e = batch_op<Pair<double>>(n, a, b, out, count, op, st); break;
-    case BINE_LONG_INT: e = batch_op<Pair<long>>(n, a, b, out, count, op, st); break;
-    case BINE_2INT: e = batch_op<Pair<int>>(n, a, b, out, count, op, st); break;
-    case BINE_SHORT_INT: e = batch_op<Pair<short>>(n, a, b, out, count, op, st); break;
-    case BINE_C_FLOAT_COMPLEX: e = batch_op<Cplx<float>>(n, a, b, out, count, op, st); break;
-    case BINE_C_DOUBLE_COMPLEX: e = batch_op<Cplx<double>>(n, a, b, out, count, op, st); break;
-#endif
-    default: return BINE_ERR_UNSUPPORTED;
-  }
-  if (e == hipErrorInvalidValue) return BINE_ERR_ARG;  // not co-aligned: caller falls back
-  return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+  return with_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    const hipError_t e =
+        with_op<T>(op, [&](auto opc) { return batch_t<T, decltype(opc)::value>(n, a, b, out, count, st); });
+    if (e == hipErrorInvalidValue) return BINE_ERR_ARG;  // not co-aligned: caller falls back
+    return status(e);
+  });
 }
 
 // system-coherent 16-B accesses of the direct transport (protocol notes at
@@ -893,12 +909,12 @@ __global__ __launch_bounds__(kBlock) void k_reduce_tree_scalar(TreeArgs t) {
     out[i] = tree_scalar<T, OP, NL>(t, i);
 }
 
-#if BINE_OPSET != 1
 // The scaled tree (bine_reduce_tree_scaled; the flagged trees of the scaled
 // collectives): sibling kernels of the three above with S applied to the final
 // value in registers -- the same loads, the same tree, the same store, one
 // multiply more per element.  Siblings, not a flag on the kernels above, so
-// that those keep their arguments and their device code.
+// that those keep their arguments and their device code.  Instantiated by
+// tree_nl for the four floating types, never in the opset-1 compilation.
 template <typename T, int OP, int NL>
 __global__ __launch_bounds__(kBlock) void k_reduce_tree_edges_sc(TreeArgs t, mul_of<T> m) {
   constexpr size_t V = 16 / sizeof(T);
@@ -927,99 +943,56 @@ __global__ __launch_bounds__(kBlock) void k_reduce_tree_scalar_sc(TreeArgs t, mu
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < t.n; i += (size_t)gridDim.x * kBlock)
     out[i] = scale1<T>(tree_scalar<T, OP, NL>(t, i), m);
 }
-#endif
 
-// sc != nullptr: the scaled siblings with multiplier *sc (the four floating
-// types only; hipErrorInvalidValue for any other)
-template <typename T, int OP, int NL>
-static hipError_t tree_nl(TreeArgs &t, hipStream_t st, const double *sc) {
+// the launches of one tree: the plain kernels, or (SC) their _sc siblings,
+// which take the multiplier as one more argument
+template <typename T, int OP, int NL, bool SC>
+static hipError_t tree_launch(const TreeArgs &t, hipStream_t st, [[maybe_unused]] mul_of<T> m) {
   constexpr int U = NL == 2 ? 8 : NL <= 8 ? 4 : 2;  // tools/tree_variants.hip: <8,4> 25.2 us, <8,2> 26.5 us
-  if (sc) {
-#if BINE_OPSET != 1
-    if constexpr (kScaleT<T>) {
-      const mul_of<T> m = (mul_of<T>)*sc;
-      if (t.vec) {
-        constexpr size_t V = 16 / sizeof(T);
-        const size_t tiles = (t.nvec + (size_t)kBlock * U - 1) / ((size_t)kBlock * U);
-        if (tiles)
-          hipLaunchKernelGGL((k_reduce_tree_sc<T, OP, NL, U>), dim3((unsigned)tiles), dim3(kBlock), 0, st, t, m);
-        if (t.head || t.head + t.nvec * V < t.n)
-          hipLaunchKernelGGL((k_reduce_tree_edges_sc<T, OP, NL>), dim3(1), dim3(kBlock), 0, st, t, m);
-      } else {
-        size_t blocks = (t.n + kBlock * 4 - 1) / (kBlock * 4);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL((k_reduce_tree_scalar_sc<T, OP, NL>), dim3((unsigned)blocks), dim3(kBlock), 0, st, t, m);
-      }
-      return hipGetLastError();
-    }
-#endif
-    return hipErrorInvalidValue;
-  }
+  constexpr size_t V = 16 / sizeof(T);
+  const dim3 blk(kBlock);
   if (t.vec) {
-    constexpr size_t V = 16 / sizeof(T);
-    const size_t tiles = (t.nvec + (size_t)kBlock * U - 1) / ((size_t)kBlock * U);
-    if (tiles) hipLaunchKernelGGL((k_reduce_tree<T, OP, NL, U>), dim3((unsigned)tiles), dim3(kBlock), 0, st, t);
-    if (t.head || t.head + t.nvec * V < t.n)
-      hipLaunchKernelGGL((k_reduce_tree_edges<T, OP, NL>), dim3(1), dim3(kBlock), 0, st, t);
+    const dim3 tiles((unsigned)((t.nvec + (size_t)kBlock * U - 1) / ((size_t)kBlock * U)));
+    if (tiles.x) {
+      if constexpr (SC) hipLaunchKernelGGL((k_reduce_tree_sc<T, OP, NL, U>), tiles, blk, 0, st, t, m);
+      else hipLaunchKernelGGL((k_reduce_tree<T, OP, NL, U>), tiles, blk, 0, st, t);
+    }
+    if (t.head || t.head + t.nvec * V < t.n) {
+      if constexpr (SC) hipLaunchKernelGGL((k_reduce_tree_edges_sc<T, OP, NL>), dim3(1), blk, 0, st, t, m);
+      else hipLaunchKernelGGL((k_reduce_tree_edges<T, OP, NL>), dim3(1), blk, 0, st, t);
+    }
   } else {
-    size_t blocks = (t.n + kBlock * 4 - 1) / (kBlock * 4);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL((k_reduce_tree_scalar<T, OP, NL>), dim3((unsigned)blocks), dim3(kBlock), 0, st, t);
+    const dim3 blocks(scalar_blocks(t.n));
+    if constexpr (SC) hipLaunchKernelGGL((k_reduce_tree_scalar_sc<T, OP, NL>), blocks, blk, 0, st, t, m);
+    else hipLaunchKernelGGL((k_reduce_tree_scalar<T, OP, NL>), blocks, blk, 0, st, t);
   }
   return hipGetLastError();
 }
 
-template <typename T, int OP>
-static hipError_t tree_t(int nl, TreeArgs &t, hipStream_t st, const double *sc) {
-  switch (nl) {
-    case 2: return tree_nl<T, OP, 2>(t, st, sc);
-    case 4: return tree_nl<T, OP, 4>(t, st, sc);
-    case 8: return tree_nl<T, OP, 8>(t, st, sc);
-    case 16: return tree_nl<T, OP, 16>(t, st, sc);
-    default: return hipErrorInvalidValue;
-  }
+// sc != nullptr: the scaled siblings with multiplier *sc (the four floating
+// types only, and not in the opset-1 compilation, which has no scaled entry
+// point; hipErrorInvalidValue otherwise)
+template <typename T, int OP, int NL>
+static hipError_t tree_nl(const TreeArgs &t, hipStream_t st, const double *sc) {
+  if (!sc) return tree_launch<T, OP, NL, false>(t, st, {});
+  if constexpr (BINE_OPSET != 1 && kScaleT<T>) return tree_launch<T, OP, NL, true>(t, st, (mul_of<T>)*sc);
+  else return hipErrorInvalidValue;
 }
 
+// fills in the split of t.n elements of T, then the tree for (op, nl)
 template <typename T>
-static hipError_t tree_op(int nl, TreeArgs &t, int op, hipStream_t st, const double *sc = nullptr) {
-  constexpr size_t V = 16 / sizeof(T);
+static hipError_t tree_op(int nl, TreeArgs &t, int op, hipStream_t st, const double *sc) {
   const uintptr_t oo = (uintptr_t)t.out;
   bool co = (oo % sizeof(T)) == 0;
   for (int j = 0; j < nl; j++) co = co && (((uintptr_t)t.leaf[j] ^ oo) & 15) == 0;
+  const VecSplit vs = co ? vec_split(oo, t.n, sizeof(T)) : VecSplit{t.n, 0};
   t.vec = co ? 1 : 0;
-  t.head = co ? std::min<uint64_t>(((16 - (oo & 15)) & 15) / sizeof(T), t.n) : t.n;
-  t.nvec = co ? (t.n - t.head) / V : 0;
-#define CALL(OP) tree_t<T, OP>(nl, t, st, sc)
-  BINE_OP_SWITCH(T, CALL)
-#undef CALL
+  t.head = vs.head;
+  t.nvec = vs.nvec;
+  return with_op<T>(op, [&](auto opc) {
+    return with_nl(nl, [&](auto nlc) { return tree_nl<T, decltype(opc)::value, decltype(nlc)::value>(t, st, sc); });
+  });
 }
-
-static int reduce_tree_run(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op, void *stream,
-                           unsigned swap, const double *sc);
-
-int BINE_FN(launch_reduce_tree)(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
-                                void *stream, unsigned swap) {
-  if (count == 0) return BINE_SUCCESS;
-#if BINE_OPSET == 0
-  if (h16_dtype(dtype)) return launch_reduce_tree_h16(nl, leaf, out, count, dtype, op, stream, swap);
-  if (ext_op(dtype, op)) return launch_reduce_tree_logic(nl, leaf, out, count, dtype, op, stream, swap);
-#endif
-  return reduce_tree_run(nl, leaf, out, count, dtype, op, stream, swap, nullptr);
-}
-
-#if BINE_OPSET != 1
-// the same tree with S applied to every final value in the same launch
-// (k_reduce_tree_sc); the caller has checked bine_scale_valid(dtype, op)
-int BINE_FN(launch_reduce_tree_scaled)(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
-                                       void *stream, unsigned swap, double scale) {
-  if (!bine_scale_valid(dtype, op)) return BINE_ERR_ARG;
-  if (count == 0) return BINE_SUCCESS;
-#if BINE_OPSET == 0
-  if (h16_dtype(dtype)) return launch_reduce_tree_scaled_h16(nl, leaf, out, count, dtype, op, stream, swap, scale);
-#endif
-  return reduce_tree_run(nl, leaf, out, count, dtype, op, stream, swap, &scale);
-}
-#endif
 
 static int reduce_tree_run(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op, void *stream,
                            unsigned swap, const double *sc) {
@@ -1033,36 +1006,36 @@ static int reduce_tree_run(int nl, const void *const *leaf, void *out, size_t co
   t.n = count * scale;
   t.swap = swap;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  switch (dtype) {
-#if BINE_OPSET == 2
-    case BINE_FLOAT16: e = tree_op<F16>(nl, t, op, st, sc); break;
-    case BINE_BFLOAT16: e = tree_op<BF16>(nl, t, op, st, sc); break;
-#else
-    case BINE_INT8: e = tree_op<int8_t>(nl, t, op, st, sc); break;
-    case BINE_UINT8: e = tree_op<uint8_t>(nl, t, op, st, sc); break;
-    case BINE_INT16: e = tree_op<int16_t>(nl, t, op, st, sc); break;
-    case BINE_UINT16: e = tree_op<uint16_t>(nl, t, op, st, sc); break;
-    case BINE_INT32: e = tree_op<int32_t>(nl, t, op, st, sc); break;
-    case BINE_UINT32: e = tree_op<uint32_t>(nl, t, op, st, sc); break;
-    case BINE_INT64: e = tree_op<int64_t>(nl, t, op, st, sc); break;
-    case BINE_UINT64: e = tree_op<uint64_t>(nl, t, op, st, sc); break;
-    case BINE_FLOAT: e = tree_op<float>(nl, t, op, st, sc); break;
-    case BINE_DOUBLE: e = tree_op<double>(nl, t, op, st, sc); break;
-#endif
-#if BINE_OPSET == 1
-    case BINE_FLOAT_INT: e = tree_op<Pair<float>>(nl, t, op, st, sc); break;
-    case BINE_DOUBLE_INT: e = tree_op<Pair<double>>(nl, t, op, st, sc); break;
-    case BINE_LONG_INT: e = tree_op<Pair<long>>(nl, t, op, st, sc); break;
-    case BINE_2INT: e = tree_op<Pair<int>>(nl, t, op, st, sc); break;
-    case BINE_SHORT_INT: e = tree_op<Pair<short>>(nl, t, op, st, sc); break;
-    case BINE_C_FLOAT_COMPLEX: e = tree_op<Cplx<float>>(nl, t, op, st, sc); break;
-    case BINE_C_DOUBLE_COMPLEX: e = tree_op<Cplx<double>>(nl, t, op, st, sc); break;
-#endif
-    default: return BINE_ERR_UNSUPPORTED;
-  }
-  return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+  return with_dtype(dtype, [&](auto tag) {
+    return status(tree_op<typename decltype(tag)::type>(nl, t, op, st, sc));
+  });
 }
+
+int BINE_FN(launch_reduce_tree)(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
+                                void *stream, unsigned swap) {
+  if (count == 0) return BINE_SUCCESS;
+#if BINE_OPSET == 0
+  if (const int o = owner_opset(dtype, op))
+    return o == 2 ? launch_reduce_tree_h16(nl, leaf, out, count, dtype, op, stream, swap)
+                  : launch_reduce_tree_logic(nl, leaf, out, count, dtype, op, stream, swap);
+#endif
+  return reduce_tree_run(nl, leaf, out, count, dtype, op, stream, swap, nullptr);
+}
+
+#if BINE_OPSET != 1
+// the same tree with S applied to every final value in the same launch
+// (k_reduce_tree_sc); the caller has checked bine_scale_valid(dtype, op)
+int BINE_FN(launch_reduce_tree_scaled)(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
+                                       void *stream, unsigned swap, double scale) {
+  if (!bine_scale_valid(dtype, op)) return BINE_ERR_ARG;
+  if (count == 0) return BINE_SUCCESS;
+#if BINE_OPSET == 0
+  if (owner_opset(dtype, op) == 2)
+    return launch_reduce_tree_scaled_h16(nl, leaf, out, count, dtype, op, stream, swap, scale);
+#endif
+  return reduce_tree_run(nl, leaf, out, count, dtype, op, stream, swap, &scale);
+}
+#endif
 
 #if BINE_OPSET != 1
 // ----------------------------------------------------------------------------
@@ -1111,19 +1084,15 @@ __global__ __launch_bounds__(kBlock) void k_scale_scalar(const T *in, T *out, si
 
 template <typename T>
 static hipError_t scale_t(const void *in, void *out, size_t n, double scale, hipStream_t st) {
-  constexpr size_t V = 16 / sizeof(T);
   const mul_of<T> m = (mul_of<T>)scale;  // (float)scale: round to nearest even
   const T *pi = (const T *)in;
   T *po = (T *)out;
   const uintptr_t io = (uintptr_t)in, oo = (uintptr_t)out;
   if (((io ^ oo) & 15) != 0 || (oo % sizeof(T)) != 0) {
-    size_t blocks = (n + kBlock * 4 - 1) / (kBlock * 4);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL((k_scale_scalar<T>), dim3((unsigned)blocks), dim3(kBlock), 0, st, pi, po, n, m);
+    hipLaunchKernelGGL((k_scale_scalar<T>), dim3(scalar_blocks(n)), dim3(kBlock), 0, st, pi, po, n, m);
     return hipGetLastError();
   }
-  const size_t head = std::min<size_t>(((16 - (oo & 15)) & 15) / sizeof(T), n);
-  const size_t nvec = (n - head) / V;
+  const auto [head, nvec] = vec_split(oo, n, sizeof(T));
   const size_t tiles = (nvec + (size_t)kBlock * kScaleU - 1) / ((size_t)kBlock * kScaleU);
   const unsigned blocks = (unsigned)(tiles ? tiles : 1);
   if (in == out) hipLaunchKernelGGL((k_scale<T, false>), dim3(blocks), dim3(kBlock), 0, st, pi, po, head, nvec, n, m);
@@ -1135,21 +1104,14 @@ int BINE_FN(launch_scale)(const void *in, void *out, size_t count, int dtype, do
   if (!bine_scale_valid(dtype, BINE_SUM)) return BINE_ERR_ARG;
   if (count == 0) return BINE_SUCCESS;
 #if BINE_OPSET == 0
-  if (h16_dtype(dtype)) return launch_scale_h16(in, out, count, dtype, scale, stream);
+  if (owner_opset(dtype, BINE_SUM) == 2) return launch_scale_h16(in, out, count, dtype, scale, stream);
 #endif
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  switch (dtype) {
-#if BINE_OPSET == 2
-    case BINE_FLOAT16: e = scale_t<F16>(in, out, count, scale, st); break;
-    case BINE_BFLOAT16: e = scale_t<BF16>(in, out, count, scale, st); break;
-#else
-    case BINE_FLOAT: e = scale_t<float>(in, out, count, scale, st); break;
-    case BINE_DOUBLE: e = scale_t<double>(in, out, count, scale, st); break;
-#endif
-    default: return BINE_ERR_ARG;
-  }
-  return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+  return with_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    if constexpr (kScaleT<T>) return status(scale_t<T>(in, out, count, scale, st));
+    else return BINE_ERR_ARG;
+  });
 }
 #endif  // BINE_OPSET != 1
 
@@ -1707,46 +1669,50 @@ __global__ __launch_bounds__(kBlock) void k_dm_move_tree(DmArgs a, DmTree t) {
   dm_launch_done(a);
 }
 
+// The element types the direct transport's in-launch reductions
+// (k_dm_move_tree, k_dm_fused) are instantiated for, with SUM / PROD / MAX /
+// MIN: the one list behind dm_fused_supported, the two launchers and
+// dm_launch_cap.
+template <typename T>
+constexpr bool kDmT = std::is_same_v<T, float> || std::is_same_v<T, double> || std::is_same_v<T, int32_t> ||
+                      std::is_same_v<T, int64_t> || std::is_same_v<T, uint32_t> || std::is_same_v<T, uint64_t>;
+
+// with_dtype restricted to those types; BINE_ERR_UNSUPPORTED for the rest
+template <typename F>
+static int with_dm_dtype(int dtype, F &&f) {
+  return with_dtype(dtype, [&](auto tag) -> int {
+    if constexpr (kDmT<typename decltype(tag)::type>) return f(tag);
+    else return BINE_ERR_UNSUPPORTED;
+  });
+}
+
+bool dm_fused_supported(int dtype, int op) {
+  return op >= BINE_SUM && op <= BINE_MIN && with_dm_dtype(dtype, [](auto) { return BINE_SUCCESS; }) == BINE_SUCCESS;
+}
+
 bool dm_tree_supported(int dtype, int op, int nl) {
-  return dm_fused_supported(dtype, op) && (nl == 2 || nl == 4 || nl == 8 || nl == 16);
+  return dm_fused_supported(dtype, op) && with_nl(nl, [](auto) { return true; }, false);
 }
 
 template <typename T, int OP>
 static const void *dmt_kernel(int nl) {
-  switch (nl) {
-    case 2: return (const void *)k_dm_move_tree<T, OP, 2>;
-    case 4: return (const void *)k_dm_move_tree<T, OP, 4>;
-    case 8: return (const void *)k_dm_move_tree<T, OP, 8>;
-    case 16: return (const void *)k_dm_move_tree<T, OP, 16>;
-    default: return nullptr;
-  }
+  return with_nl(nl, [](auto nlc) { return (const void *)k_dm_move_tree<T, OP, decltype(nlc)::value>; },
+                 (const void *)nullptr);
 }
 
 template <typename T, int OP>
 static hipError_t dmt_launch(const DmArgs &a0, const DmTree &t0, hipStream_t st) {
-  DmArgs a = a0;
-  DmTree t = t0;
-  if (const void *k = dmt_kernel<T, OP>(t.nl))
-    if (dm_fit_residency(a.cwgs, a.ncopy, &t.twgs, dm_cap(k, a.share)) > 0) {
+  return with_nl(t0.nl, [&](auto nlc) {
+    constexpr int NL = decltype(nlc)::value;
+    DmArgs a = a0;
+    DmTree t = t0;
+    if (dm_fit_residency(a.cwgs, a.ncopy, &t.twgs, dm_cap((const void *)k_dm_move_tree<T, OP, NL>, a.share)) > 0) {
       a.ncw = 0;
       for (int c = 0; c < a.ncopy; c++) a.ncw += a.cwgs[c];
     }
-  const dim3 g((unsigned)(a.ncw + t.twgs));
-  switch (t.nl) {
-    case 2: hipLaunchKernelGGL((k_dm_move_tree<T, OP, 2>), g, dim3(kBlock), 0, st, a, t); break;
-    case 4: hipLaunchKernelGGL((k_dm_move_tree<T, OP, 4>), g, dim3(kBlock), 0, st, a, t); break;
-    case 8: hipLaunchKernelGGL((k_dm_move_tree<T, OP, 8>), g, dim3(kBlock), 0, st, a, t); break;
-    case 16: hipLaunchKernelGGL((k_dm_move_tree<T, OP, 16>), g, dim3(kBlock), 0, st, a, t); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t dmt_t(const DmArgs &a, const DmTree &t, int op, hipStream_t st) {
-#define CALL(OP) dmt_launch<T, OP>(a, t, st)
-  BINE_OP_SWITCH(T, CALL)
-#undef CALL
+    hipLaunchKernelGGL((k_dm_move_tree<T, OP, NL>), dim3((unsigned)(a.ncw + t.twgs)), dim3(kBlock), 0, st, a, t);
+    return hipGetLastError();
+  });
 }
 
 int launch_dm_move_tree(const DmArgs &a, const DmTree &t, int dtype, int op, void *stream) {
@@ -1767,17 +1733,10 @@ int launch_dm_move_tree(const DmArgs &a, const DmTree &t, int dtype, int op, voi
     seen |= 1ull << i;
   }
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  switch (dtype) {
-    case BINE_FLOAT: e = dmt_t<float>(a, t, op, st); break;
-    case BINE_DOUBLE: e = dmt_t<double>(a, t, op, st); break;
-    case BINE_INT32: e = dmt_t<int32_t>(a, t, op, st); break;
-    case BINE_INT64: e = dmt_t<int64_t>(a, t, op, st); break;
-    case BINE_UINT32: e = dmt_t<uint32_t>(a, t, op, st); break;
-    case BINE_UINT64: e = dmt_t<uint64_t>(a, t, op, st); break;
-    default: return BINE_ERR_UNSUPPORTED;
-  }
-  return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+  return with_dm_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return status(with_op<T>(op, [&](auto opc) { return dmt_launch<T, decltype(opc)::value>(a, t, st); }));
+  });
 }
 
 // ----------------------------------------------------------------------------
@@ -2114,19 +2073,6 @@ static hipError_t fused_launch(const DmFusedArgs &a0, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t fused_t(const DmFusedArgs &a, int op, hipStream_t st) {
-#define CALL(OP) fused_launch<T, OP>(a, st)
-  BINE_OP_SWITCH(T, CALL)
-#undef CALL
-}
-
-bool dm_fused_supported(int dtype, int op) {
-  const bool t = dtype == BINE_FLOAT || dtype == BINE_DOUBLE || dtype == BINE_INT32 || dtype == BINE_INT64 ||
-                 dtype == BINE_UINT32 || dtype == BINE_UINT64;
-  return t && op >= BINE_SUM && op <= BINE_MIN;
-}
-
 int dm_fused_check(const DmFusedArgs &a, int dtype, int op) {
   if (!dm_fused_supported(dtype, op)) return BINE_ERR_UNSUPPORTED;
   const int nm = a.d0 + a.nd;
@@ -2170,17 +2116,10 @@ int dm_fused_check(const DmFusedArgs &a, int dtype, int op) {
 int launch_dm_fused(const DmFusedArgs &a, int dtype, int op, void *stream) {
   if (int rc = dm_fused_check(a, dtype, op)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  switch (dtype) {
-    case BINE_FLOAT: e = fused_t<float>(a, op, st); break;
-    case BINE_DOUBLE: e = fused_t<double>(a, op, st); break;
-    case BINE_INT32: e = fused_t<int32_t>(a, op, st); break;
-    case BINE_INT64: e = fused_t<int64_t>(a, op, st); break;
-    case BINE_UINT32: e = fused_t<uint32_t>(a, op, st); break;
-    case BINE_UINT64: e = fused_t<uint64_t>(a, op, st); break;
-    default: return BINE_ERR_UNSUPPORTED;
-  }
-  return e == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+  return with_dm_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return status(with_op<T>(op, [&](auto opc) { return fused_launch<T, decltype(opc)::value>(a, st); }));
+  });
 }
 
 // ----------------------------------------------------------------------------
@@ -2290,22 +2229,11 @@ int launch_fill_pico(void *buf, size_t n, int dtype, uint32_t seed, void *stream
   hipStream_t st = (hipStream_t)stream;
   const size_t lanes = (n + kFillPer - 1) / kFillPer;
   const unsigned blocks = (unsigned)((lanes + kBlock - 1) / kBlock);
-#define FILL(T, DT) hipLaunchKernelGGL((k_fill_pico<T, DT>), dim3(blocks), dim3(kBlock), 0, st, (T *)buf, n, seed); break
-  switch (dtype) {
-    case BINE_INT8: FILL(int8_t, BINE_INT8);
-    case BINE_UINT8: FILL(uint8_t, BINE_UINT8);
-    case BINE_INT16: FILL(int16_t, BINE_INT16);
-    case BINE_UINT16: FILL(uint16_t, BINE_UINT16);
-    case BINE_INT32: FILL(int32_t, BINE_INT32);
-    case BINE_UINT32: FILL(uint32_t, BINE_UINT32);
-    case BINE_INT64: FILL(int64_t, BINE_INT64);
-    case BINE_UINT64: FILL(uint64_t, BINE_UINT64);
-    case BINE_FLOAT: FILL(float, BINE_FLOAT);
-    case BINE_DOUBLE: FILL(double, BINE_DOUBLE);
-    default: return BINE_ERR_UNSUPPORTED;
-  }
-#undef FILL
-  return hipGetLastError() == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((k_fill_pico<T, decltype(tag)::id>), dim3(blocks), dim3(kBlock), 0, st, (T *)buf, n, seed);
+    return status(hipGetLastError());
+  });
 }
 
 // ----------------------------------------------------------------------------
@@ -2371,35 +2299,19 @@ int launch_checksum(const void *buf, size_t n, int dtype, uint64_t *host_out, vo
 // workgroup slots of the current device for one direct-transport kernel
 // (bine_dm_launch_cap): kind 0 k_dm_move, 1 k_dm_move_tree<T, OP, nl>,
 // 2 k_dm_fused<T, OP>; T / OP from (dtype, op) as the launchers pick them
-template <typename T>
-static const void *dm_kernel_t(int kind, int op, int nl) {
-  auto pick = [&](auto opc) -> const void * {
-    constexpr int OP = decltype(opc)::value;
-    return kind == 1 ? dmt_kernel<T, OP>(nl) : (const void *)k_dm_fused<T, OP>;
-  };
-  switch (op) {
-    case BINE_SUM: return pick(std::integral_constant<int, BINE_SUM>{});
-    case BINE_PROD: return pick(std::integral_constant<int, BINE_PROD>{});
-    case BINE_MAX: return pick(std::integral_constant<int, BINE_MAX>{});
-    case BINE_MIN: return pick(std::integral_constant<int, BINE_MIN>{});
-    default: return nullptr;
-  }
-}
-
 int dm_launch_cap(int kind, int dtype, int op, int nl, int share) {
   const void *k = nullptr;
   if (kind == 0) {
     k = (const void *)k_dm_move;
   } else if (kind == 1 || kind == 2) {
-    switch (dtype) {
-      case BINE_FLOAT: k = dm_kernel_t<float>(kind, op, nl); break;
-      case BINE_DOUBLE: k = dm_kernel_t<double>(kind, op, nl); break;
-      case BINE_INT32: k = dm_kernel_t<int32_t>(kind, op, nl); break;
-      case BINE_INT64: k = dm_kernel_t<int64_t>(kind, op, nl); break;
-      case BINE_UINT32: k = dm_kernel_t<uint32_t>(kind, op, nl); break;
-      case BINE_UINT64: k = dm_kernel_t<uint64_t>(kind, op, nl); break;
-      default: break;
-    }
+    with_dm_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      k = with_op<T>(op, [&](auto opc) {
+        constexpr int OP = decltype(opc)::value;
+        return kind == 1 ? dmt_kernel<T, OP>(nl) : (const void *)k_dm_fused<T, OP>;
+      }, (const void *)nullptr);
+      return BINE_SUCCESS;
+    });
   }
   return k ? dm_cap(k, share) : -1;
 }
