@@ -247,6 +247,62 @@ int bine_scale(const void *in, void *out, size_t count, int dtype, double scale,
 /* bine_reduce_tree_swap's result with S applied, in the same launch */
 int bine_reduce_tree_scaled(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
                             unsigned swap, double scale, void *stream);
+/* ---- wide (binary32-accumulating) reductions of the 16-bit types -----------------
+ * A wide call is defined for dtype BINE_FLOAT16 or BINE_BFLOAT16 and op SUM,
+ * PROD, MAX or MIN.  Let X_r be rank r's input widened exactly to binary32,
+ * element for element, and F what the existing binary32 call returns for X on
+ * the same algorithm, arguments and communicator settings (flat / literal
+ * forms, multi-tree mode, chunk): bine_allreduce / bine_reduce_scatter /
+ * bine_reduce_tree_swap with BINE_FLOAT when scale == 1.0, otherwise
+ * bine_allreduce_scaled / bine_reduce_scatter_scaled / bine_reduce_tree_scaled
+ * with BINE_FLOAT and the same `scale`.  The wide call returns narrow(F): F
+ * rounded to nearest even into the 16-bit format, subnormals kept on input and
+ * output, overflow giving +-inf, a NaN giving a NaN of unspecified payload --
+ * and nothing else, whatever path computes it.  Every pairwise reduction is
+ * thus a binary32 operation and each output element is rounded to 16 bits
+ * ONCE (the plain 16-bit calls round at every level of the tree, by their own
+ * contract above; their bits do not change).  The statuses are those of the
+ * binary32 call.  Every other (dtype, op) pair is BINE_ERR_ARG, returned on
+ * every rank before any exchange and before any HIP call.
+ *
+ * Two paths compute it, chosen by the planner alone, never by the transport
+ * (bine_plan_wide says which):
+ *   A  k_widen of the input into a binary32 workspace the communicator owns
+ *      (grown like its other workspaces and reused), the binary32 (scaled)
+ *      call on that workspace -- in place when the wide call is in place, else
+ *      from one region of it into another -- and k_narrow of its output into
+ *      rbuf.  Any P, algorithm, transport and mode.
+ *   B  where every reduction of the call is a final REDUCE_TREE -- exactly
+ *      where a scaled call's trees carry BINE_PRIM_SCALED: the flat
+ *      reduce-scatter forms at power-of-two P <= 16 and the one-shot latency
+ *      forms; not the rings' folded chain, multi-tree mode, non-power-of-two
+ *      P or P = 1 -- the call is planned with the 16-bit element size (blocks,
+ *      chunks and exchanges carry 16-bit data: half the bytes of path A and no
+ *      conversion pass) and every such tree carries BINE_PRIM_WIDE: its
+ *      leaves are widened in registers, the reference's tree is evaluated
+ *      level by level in binary32 with the plain tree's association, operand
+ *      order and swap bits, one binary32 multiplication by (float)scale
+ *      follows (by 1.0f when scale == 1.0: the identity on every non-NaN
+ *      value) and one nearest-even narrowing precedes the store.
+ * The binary32 flat forms are bit-identical to the binary32 literal schedule,
+ * so A and B give the same bits.  BINE_WIDE_TREES=0 in the environment (read
+ * at every call) forces path A.  Graph mode: a path-B call's graphs are keyed
+ * on the entry point and the scale's bits; on path A the conversions run
+ * eagerly around the binary32 call, which is captured and replayed as any
+ * other.  Not provided: bine_reduce, the staged host-buffer entry points, the
+ * libbine.h drop-in. */
+/* 1 exactly on {FLOAT16, BFLOAT16} x {SUM, PROD, MAX, MIN} */
+int bine_wide_valid(int dtype, int op);
+/* out32[i] = in16[i] widened exactly (binary32); out16[i] = in32[i] rounded to
+ * nearest even into `dtype` (BINE_FLOAT16 / BINE_BFLOAT16, else BINE_ERR_ARG).
+ * The operands must not overlap; any alignment bine_reduce3 accepts. */
+int bine_widen(const void *in16, void *out32, size_t count, int dtype, void *stream);
+int bine_narrow(const void *in32, void *out16, size_t count, int dtype, void *stream);
+/* narrow(bine_reduce_tree_swap / _scaled's BINE_FLOAT result on the widened
+ * leaves) in one launch (k_reduce_tree_wide); `out` may alias any leaf element
+ * for element */
+int bine_reduce_tree_wide(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
+                          unsigned swap, double scale, void *stream);
 /* copy_buffer on the device (libbine_utils.h:176-190; the sbuf -> rbuf copy of
  * e.g. allreduce_bine_bdw_remap, libbine_allreduce.c:849-852): dst[0:bytes) =
  * src[0:bytes), stream-ordered, the kernel every COPY primitive runs. */
@@ -569,6 +625,12 @@ int bine_allreduce_scaled(bine_comm_t comm, int algo, const void *sbuf, void *rb
                           int dtype, int op, double scale, size_t segsize, void *stream);
 int bine_reduce_scatter_scaled(bine_comm_t comm, int algo, const void *sbuf, void *rbuf,
                                const int *rcounts, int dtype, int op, double scale, void *stream);
+/* the wide forms (see "wide reductions" above): narrow(the BINE_FLOAT call's
+ * result on the widened inputs); dtype BINE_FLOAT16 / BINE_BFLOAT16 */
+int bine_allreduce_wide(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
+                        int dtype, int op, double scale, size_t segsize, void *stream);
+int bine_reduce_scatter_wide(bine_comm_t comm, int algo, const void *sbuf, void *rbuf,
+                             const int *rcounts, int dtype, int op, double scale, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -635,6 +697,13 @@ int bine_loopback_run_reduce_scatter_scaled(bine_comm_t *comms, int nranks, int 
                                             const void *const *sbufs, void *const *rbufs,
                                             const int *rcounts, int dtype, int op, double scale,
                                             int *statuses);
+int bine_loopback_run_allreduce_wide(bine_comm_t *comms, int nranks, int algo,
+                                     const void *const *sbufs, void *const *rbufs, size_t count,
+                                     int dtype, int op, double scale, size_t segsize, int *statuses);
+int bine_loopback_run_reduce_scatter_wide(bine_comm_t *comms, int nranks, int algo,
+                                          const void *const *sbufs, void *const *rbufs,
+                                          const int *rcounts, int dtype, int op, double scale,
+                                          int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);
@@ -668,13 +737,17 @@ typedef enum { BINE_BUF_SBUF = 0, BINE_BUF_RBUF = 1, BINE_BUF_TMP0 = 2, BINE_BUF
 #define BINE_PRIM_SCALED 2    /* flags, REDUCE_TREE of a scaled call: the tree's output is
                                  final and is multiplied by the call's scale before
                                  it is stored */
+#define BINE_PRIM_WIDE 4      /* flags, REDUCE_TREE of a wide call (path B): the tree's output is
+                                 final; it is evaluated in binary32 on the widened 16-bit
+                                 leaves, multiplied by the call's scale and narrowed once
+                                 before it is stored */
 /* REDUCE_TREE: flags >> 8 = levels whose combine is v[i + w] (op) v[i] (the
    right subtree is the inout side; block_by_block's last step) */
 typedef struct {
   int32_t type;      /* bine_prim_type_t */
   int32_t group;     /* consecutive SEND/RECV with equal group form one exchange */
   int32_t peer;      /* SEND/RECV peer rank; REDUCE_TREE: number of leaves nl */
-  int32_t flags;     /* BINE_PRIM_PIPELINE, BINE_PRIM_SCALED */
+  int32_t flags;     /* BINE_PRIM_PIPELINE, BINE_PRIM_SCALED, BINE_PRIM_WIDE */
   int32_t src_buf;   /* SEND: source; REDUCE/REDUCE3: `in` (a); COPY: source;
                         REDUCE_TREE: the other nl-1 leaves, k-th at src_off + k*count */
   int32_t dst_buf;   /* RECV: destination; REDUCE: inout; REDUCE3 / REDUCE_TREE: out; COPY: dest */
@@ -722,8 +795,12 @@ int64_t bine_plan(int algo, int nranks, int rank, size_t count, const int *rcoun
  * pair as one out-of-place k_scale.)  This is the RCCL / loopback form; over
  * the direct transport a call whose trees run inside the transport's
  * launches runs the unscaled schedule plus a trailing scale.  Without bit 4
- * the output is what it always was.  Returns the number of entries (may
- * exceed cap) or -status. */
+ * the output is what it always was.  Bit 5 (32) = the call is wide
+ * (bine_allreduce_wide / bine_reduce_scatter_wide; esz = 2): a path-B call's
+ * schedule equals the plain 16-bit schedule op for op and wait for wait,
+ * except that every final REDUCE_TREE carries BINE_PRIM_WIDE; a path-A call
+ * has no wide schedule (BINE_ERR_UNSUPPORTED); bits 4 and 5 together are
+ * BINE_ERR_ARG.  Returns the number of entries (may exceed cap) or -status. */
 typedef struct {
   int32_t op;
   int32_t xchg;
@@ -735,6 +812,13 @@ int64_t bine_plan_schedule(int algo, int nranks, int rank, size_t count, const i
                            size_t esz, size_t segsize, int in_place, size_t chunk_bytes,
                            size_t relay_min_bytes, int mode, bine_sched_entry_t *out, int64_t cap,
                            int *c_join, int64_t *final_wait, uint64_t *workspace);
+
+/* Which path a wide call takes (host only): 1 = path B (flagged trees), 0 =
+ * path A (through binary32), -status where the call's plan fails.  `mode` as
+ * in bine_plan_schedule (bits 0..3); the answer depends on (algorithm,
+ * nranks, counts, mode) alone, never on the rank or the transport.
+ * BINE_WIDE_TREES=0 is not consulted here. */
+int bine_plan_wide(int algo, int nranks, size_t count, const int *rcounts, int mode);
 
 /* The host staging of that schedule (bine_allreduce_staged, no relay):
  * kind 0 = host->device pieces (op, lo, hi) in elements of the input buffer,

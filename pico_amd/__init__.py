@@ -16,6 +16,13 @@ scale=s)`` return the unscaled call's bits times ``s`` (one multiplication per
 element, defined in include/bine_amd.h), ``op="avg"`` is ``op="sum",
 scale=1/comm.size``; floating types with sum / prod / max / min.  ``scale()``
 is the arithmetic on its own.
+
+Wide forms of the 16-bit types: ``allreduce_wide`` / ``reduce_scatter_wide``
+(and ``reduce_tree_wide``, ``widen``, ``narrow``) reduce float16 / bfloat16
+buffers with every pairwise operation in binary32 and ONE rounding to 16 bits
+per output element: exactly the float32 call's result on the widened inputs,
+rounded to nearest even.  ``wide_plan`` says which of the two bit-identical
+paths a call takes.
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

@@ -76,7 +76,7 @@ class OpTime(ctypes.Structure):
 
 PRIM_NAMES = {1: "SEND", 2: "RECV", 3: "REDUCE", 4: "REDUCE3", 5: "COPY", 6: "REDUCE_TREE", 7: "SCALE"}
 # bine_prim_t.flags
-PRIM_PIPELINE, PRIM_SCALED = 1, 2
+PRIM_PIPELINE, PRIM_SCALED, PRIM_WIDE = 1, 2, 4
 
 
 class BineError(RuntimeError):
@@ -158,6 +158,15 @@ def lib():
         "bine_reduce_scatter_scaled": ([vp, i, vp, vp, vp, i, i, ctypes.c_double, vp], i),
         "bine_loopback_run_allreduce_scaled": ([vp, i, i, vp, vp, sz, i, i, ctypes.c_double, sz, vp], i),
         "bine_loopback_run_reduce_scatter_scaled": ([vp, i, i, vp, vp, vp, i, i, ctypes.c_double, vp], i),
+        "bine_wide_valid": ([i, i], i),
+        "bine_widen": ([vp, vp, sz, i, vp], i),
+        "bine_narrow": ([vp, vp, sz, i, vp], i),
+        "bine_reduce_tree_wide": ([i, vp, vp, sz, i, i, ctypes.c_uint, ctypes.c_double, vp], i),
+        "bine_allreduce_wide": ([vp, i, vp, vp, sz, i, i, ctypes.c_double, sz, vp], i),
+        "bine_reduce_scatter_wide": ([vp, i, vp, vp, vp, i, i, ctypes.c_double, vp], i),
+        "bine_loopback_run_allreduce_wide": ([vp, i, i, vp, vp, sz, i, i, ctypes.c_double, sz, vp], i),
+        "bine_loopback_run_reduce_scatter_wide": ([vp, i, i, vp, vp, vp, i, i, ctypes.c_double, vp], i),
+        "bine_plan_wide": ([i, i, sz, vp, i], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

@@ -367,6 +367,93 @@ def reduce_scatter(algo, sbuf, rbuf, rcounts: Sequence[int], dtype, op: str, com
                                     _dtype(dtype, rbuf), OPS[op], _stream(stream, comm)), f"reduce_scatter_{algo}")
 
 
+# ---- wide (binary32-accumulating) forms of the 16-bit types ---------------------
+
+def wide_valid(dtype, op: str) -> bool:
+    """whether the wide calls accept (dtype, op): float16 / bfloat16 with sum /
+    prod / max / min (bine_wide_valid)"""
+    return bool(lib().bine_wide_valid(_dtype(dtype), OPS[op]))
+
+
+def widen(inbuf, outbuf, count: int, dtype=None, stream=None) -> None:
+    """outbuf (float32)[i] = inbuf (float16 / bfloat16)[i], exactly (bine_widen)"""
+    check(lib().bine_widen(_ptr(inbuf), _ptr(outbuf), count, _dtype(dtype, inbuf), _stream(stream, None)),
+          "bine_widen")
+
+
+def narrow(inbuf, outbuf, count: int, dtype=None, stream=None) -> None:
+    """outbuf (float16 / bfloat16)[i] = inbuf (float32)[i] rounded to nearest even
+    (bine_narrow)"""
+    check(lib().bine_narrow(_ptr(inbuf), _ptr(outbuf), count, _dtype(dtype, outbuf), _stream(stream, None)),
+          "bine_narrow")
+
+
+def reduce_tree_wide(leaves, out, count: int, dtype, op: str = "sum", stream=None, swap: int = 0,
+                     scale: float = 1.0) -> int:
+    """bine_reduce_tree_wide: the tree over the 16-bit leaves evaluated in
+    binary32, times float32(scale), narrowed once.  Returns the status."""
+    return lib().bine_reduce_tree_wide(len(leaves), _ptrs(leaves), _ptr(out), count, _dtype(dtype, out), OPS[op],
+                                       swap, float(scale), _stream(stream, None))
+
+
+def _wide_scale(op: str, scale, comm: Comm):
+    op, scale = _scaled(op, scale, comm)
+    return op, 1.0 if scale is None else float(scale)
+
+
+def allreduce_wide(algo, sbuf, rbuf, count: int, dtype, op: str, comm: Comm, segsize: int = 0, stream=None,
+                   scale=None) -> None:
+    """bine_allreduce_wide: float16 / bfloat16 buffers, every pairwise reduction
+    in binary32, one rounding to 16 bits per output element; scale / op="avg"
+    as allreduce's"""
+    op, scale = _wide_scale(op, scale, comm)
+    check(lib().bine_allreduce_wide(comm.handle, _algo("allreduce", algo), _ptr(sbuf), _ptr(rbuf), count,
+                                    _dtype(dtype, rbuf), OPS[op], scale, segsize, _stream(stream, comm)),
+          f"allreduce_{algo} (wide)")
+
+
+def reduce_scatter_wide(algo, sbuf, rbuf, rcounts: Sequence[int], dtype, op: str, comm: Comm, stream=None,
+                        scale=None) -> None:
+    """bine_reduce_scatter_wide (see allreduce_wide)"""
+    rc = (ctypes.c_int * len(rcounts))(*rcounts)
+    op, scale = _wide_scale(op, scale, comm)
+    check(lib().bine_reduce_scatter_wide(comm.handle, _algo("reduce_scatter", algo), _ptr(sbuf), _ptr(rbuf), rc,
+                                         _dtype(dtype, rbuf), OPS[op], scale, _stream(stream, comm)),
+          f"reduce_scatter_{algo} (wide)")
+
+
+def loopback_allreduce_wide(comms, algo, sbufs, rbufs, count, dtype, op="sum", segsize=0, scale=None):
+    st = (ctypes.c_int * len(comms))()
+    hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
+    op, scale = _wide_scale(op, scale, comms[0])
+    rc = lib().bine_loopback_run_allreduce_wide(hs, len(comms), _algo("allreduce", algo), _ptrs(sbufs), _ptrs(rbufs),
+                                                count, _dtype(dtype, rbufs[0]), OPS[op], scale, segsize, st)
+    return rc, list(st)
+
+
+def loopback_reduce_scatter_wide(comms, algo, sbufs, rbufs, rcounts, dtype, op="sum", scale=None):
+    st = (ctypes.c_int * len(comms))()
+    hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
+    rcs = (ctypes.c_int * len(rcounts))(*rcounts)
+    op, scale = _wide_scale(op, scale, comms[0])
+    rc = lib().bine_loopback_run_reduce_scatter_wide(hs, len(comms), _algo("reduce_scatter", algo), _ptrs(sbufs),
+                                                     _ptrs(rbufs), rcs, _dtype(dtype, rbufs[0]), OPS[op], scale, st)
+    return rc, list(st)
+
+
+def wide_plan(coll: str, algo, nranks: int, count: int = 0, rcounts=None, trees: bool = False,
+              flat_ag=False, flat_rs: bool = False) -> bool:
+    """Which path a wide call takes (bine_plan_wide, host only): True = path B
+    (the 16-bit plan with BINE_PRIM_WIDE trees), False = path A (through
+    binary32).  Raises BineError where the call's plan fails."""
+    rc = (ctypes.c_int * nranks)(*rcounts) if rcounts is not None else None
+    mode = int(trees) | (2 if flat_ag else 0) | (4 if flat_rs else 0) | (8 if flat_ag == 2 else 0)
+    r = lib().bine_plan_wide(_algo(coll, algo), nranks, count, rc, mode)
+    if r < 0:
+        raise BineError(-r, f"wide_plan {coll}_{algo}")
+    return bool(r)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -461,10 +548,11 @@ def plan(coll: str, algo, nranks: int, rank: int, count: int = 0, rcounts=None, 
 def schedule(coll: str, algo, nranks: int, rank: int, count: int = 0, rcounts=None, root: int = 0,
              esz: int = 4, segsize: int = 0, in_place: bool = False, chunk_bytes: int = 0,
              relay_min_bytes: int = 0, info: bool = False, trees: bool = False, flat_ag: bool = False,
-             flat_rs: bool = False, scaled: bool = False):
+             flat_rs: bool = False, scaled: bool = False, wide: bool = False):
     """The executor's two-stream issue schedule of rank `rank` (host only).
     scaled=True: of the scaled call (flagged trees, flags & PRIM_SCALED, or one
-    trailing "SCALE").
+    trailing "SCALE").  wide=True (esz=2): of a path-B wide call (its final
+    trees carry flags & PRIM_WIDE); a path-A call raises ERR_UNSUPPORTED.
     Returns (ops, c_join, final_wait); ops[i] = {"xchg", "wait", "prims"}.
     With info=True a 4th item: {"tmp_elems": [TMP0..2], "stage_elems": relay staging}."""
     a = _algo(coll, algo)
@@ -472,7 +560,7 @@ def schedule(coll: str, algo, nranks: int, rank: int, count: int = 0, rcounts=No
     cj, fw, ws = ctypes.c_int(), ctypes.c_int64(), (ctypes.c_uint64 * 4)()
     args = (a, nranks, rank, count, rc, root, esz, segsize, int(in_place), chunk_bytes, relay_min_bytes,
             int(trees) | (2 if flat_ag else 0) | (4 if flat_rs else 0) | (8 if flat_ag == 2 else 0) |
-            (16 if scaled else 0))
+            (16 if scaled else 0) | (32 if wide else 0))
     n = lib().bine_plan_schedule(*args, None, 0, ctypes.byref(cj), ctypes.byref(fw), ws)
     if n < 0:
         raise BineError(int(-n), f"schedule {coll}_{algo}")
@@ -751,7 +839,9 @@ ENTRY_POINTS["scatter_bine"] = lambda sbuf, rbuf, count, dtype, root, comm, stre
 globals().update(ENTRY_POINTS)
 
 __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fused_msgs", "reduce_local", "reduce3", "fill_pico", "checksum", "copy",
-           "rccl_version", "scale", "scale_valid",
+           "rccl_version", "scale", "scale_valid", "wide_valid", "widen", "narrow", "reduce_tree_wide",
+           "allreduce_wide", "reduce_scatter_wide", "loopback_allreduce_wide", "loopback_reduce_scatter_wide",
+           "wide_plan",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

@@ -20,6 +20,7 @@ struct Plan {
   uint64_t tmp_elems[3] = {0, 0, 0};  // workspace per TMP buffer, elements
   int status = BINE_SUCCESS;          // non-success: the reference's error return
   bool scale_fused = false;           // scaled call: the flagged trees scale, no trailing SCALE
+  bool wide_a = false;                // wide call without covering trees: status UNSUPPORTED, take path A
 };
 
 struct PlanArgs {
@@ -66,10 +67,17 @@ struct PlanArgs {
   // Which of the two a call gets depends on (algorithm, P, counts, forms)
   // alone, never on the rank: no element is scaled twice or not at all.
   bool scaled = false;
+  // wide call (bine_allreduce_wide / bine_reduce_scatter_wide), planned with
+  // the 16-bit element size: the trees `scaled` would flag carry
+  // BINE_PRIM_WIDE instead (binary32 in registers, the call's scale, one
+  // narrowing) and Plan::scale_fused says that they cover the output -- path
+  // B.  A plan without them is no wide plan: the caller takes path A.
+  bool wide = false;
 };
 
 Plan make_plan(const PlanArgs &a);
 void append_scale(Plan &p, const PlanArgs &a);  // the trailing SCALE of a scaled call (unless p.scale_fused)
+void wide_or_path_a(Plan &p);  // a wide call's plan without covering trees: UNSUPPORTED + Plan::wide_a
 
 // multi-tree mode (trees.cpp): P-1 relabelled instances on P-1 slices; status
 // BINE_ERR_UNSUPPORTED when not applicable (only allreduce, P = 4 or 8)
@@ -179,6 +187,15 @@ int launch_reduce_tree_scaled(int nl, const void *const *leaf, void *out, size_t
                               void *stream, unsigned swap, double scale);
 int launch_reduce_tree_scaled_h16(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
                                   void *stream, unsigned swap, double scale);
+// wide (binary32-accumulating) reductions of float16 / bfloat16, opset 2 only:
+// out32[i] = in16[i] exactly (k_widen), out16[i] = nearest-even(in32[i])
+// (k_narrow), and the tree evaluated in binary32 with one multiplication by
+// (float)scale and one narrowing before the store (k_reduce_tree_wide).
+// BINE_ERR_ARG unless bine_wide_valid(dtype, op).
+int launch_widen_h16(const void *in16, void *out32, size_t count, int dtype, void *stream);
+int launch_narrow_h16(const void *in32, void *out16, size_t count, int dtype, void *stream);
+int launch_reduce_tree_wide_h16(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
+                                void *stream, unsigned swap, double scale);
 // copy_buffer on the device (k_copy); hipMemcpyAsync when src / dst are not
 // co-aligned mod 16 B
 int launch_copy(void *dst, const void *src, size_t bytes, void *stream);

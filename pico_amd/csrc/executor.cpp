@@ -522,6 +522,10 @@ struct bine_comm {
   // per-op device timing of the latest collective (bine_comm_set_profile)
   bool profile = false;
   double call_scale = 1.0;  // the scale of the scaled call being issued (under mu; flagged trees, SCALE)
+  // binary32 workspace of the wide calls' path A (bine_allreduce_wide): grown
+  // like tmp[], reused across calls
+  void *wide_ws = nullptr;
+  size_t wide_ws_bytes = 0;
   struct OpTime { hipEvent_t a = nullptr, b = nullptr; int xchg = 0, nprims = 0; uint64_t bytes = 0; };
   std::vector<OpTime> prof;
   size_t prof_n = 0;
@@ -543,6 +547,7 @@ struct bine_comm {
     tx.reset();
     for (int t = 0; t < 4; t++)
       if (tmp[t]) (void)hipFree(tmp[t]);
+    if (wide_ws) (void)hipFree(wide_ws);
     for (auto e : ev) (void)hipEventDestroy(e);
     if (order_ev) (void)hipEventDestroy(order_ev);
     for (auto &p : prof) {
@@ -797,7 +802,10 @@ static int run_local(const std::vector<Prim> &prims, Ptr ptr, int dtype, int op,
       const void *leaf[kMaxLeaves];
       for (int j = 0, k = 0; j < p.peer; j++)
         leaf[j] = j == p.pos ? ptr(p.aux_buf, p.aux_off) : ptr(p.src_buf, p.src_off + (uint64_t)k++ * p.count);
-      if (p.flags & BINE_PRIM_SCALED)  // a scaled call's final tree: S in the same launch
+      if (p.flags & BINE_PRIM_WIDE)  // a wide call's final tree: binary32 levels, the scale, one narrowing
+        rc = launch_reduce_tree_wide_h16(p.peer, leaf, ptr(p.dst_buf, p.dst_off), p.count, dtype, op, K,
+                                         (unsigned)p.flags >> 8, scale);
+      else if (p.flags & BINE_PRIM_SCALED)  // a scaled call's final tree: S in the same launch
         rc = launch_reduce_tree_scaled(p.peer, leaf, ptr(p.dst_buf, p.dst_off), p.count, dtype, op, K,
                                        (unsigned)p.flags >> 8, scale);
       else
@@ -898,7 +906,7 @@ static bool build_fused(const FusedEnv &e, OpSpan ops, Ptr ptr, size_t esz, int 
   size_t C = 0, i = 0;
   while (i + 1 < nops && ops[i].xchg && !ops[i + 1].xchg) {
     if (ops[i + 1].prims.size() != 1 || ops[i + 1].prims[0].type != BINE_PRIM_REDUCE_TREE) return false;
-    if (ops[i + 1].prims[0].flags & BINE_PRIM_SCALED) return false;  // k_dm_fused has no scale epilogue
+    if (ops[i + 1].prims[0].flags & (BINE_PRIM_SCALED | BINE_PRIM_WIDE)) return false;  // k_dm_fused has no epilogue
     C++;
     i += 2;
   }
@@ -1196,7 +1204,7 @@ static bool plan_dm_trees(const Transport &tx, bool on, const Schedule &sc, Ptr 
         sc.ops[j].prims[0].type != BINE_PRIM_REDUCE_TREE)
       continue;
     const Prim &t = sc.ops[j].prims[0];
-    if (t.flags & BINE_PRIM_SCALED) continue;  // k_dm_move_tree has no scale epilogue: a separate launch
+    if (t.flags & (BINE_PRIM_SCALED | BINE_PRIM_WIDE)) continue;  // k_dm_move_tree has no epilogue: a separate launch
     // the staging buffer: only receives write it, only trees read it
     if (t.src_buf < 0 || t.src_buf >= 8 || !clean_buf[t.src_buf]) continue;
     TreeSpec ts;
@@ -1511,6 +1519,7 @@ static std::string plan_key(const PlanArgs &a) {
            a.root, (int)a.flat_ag, (int)a.flat_ag_chunked, (int)a.flat_rs);
   k = buf;
   if (a.scaled) k += "S|";
+  if (a.wide) k += "W|";
   for (int x : a.rcounts) { k += std::to_string(x); k += ','; }
   return k;
 }
@@ -1520,7 +1529,8 @@ static void build(const PlanArgs &args, size_t ch, size_t relay_min_bytes, bool 
   PlanArgs a = args;
   a.flat_chunk = ch;  // the flat reduce-scatter is chunked by the planner itself
   if (trees) plan = make_tree_plan(a);
-  if (!trees || plan.status == BINE_ERR_UNSUPPORTED) plan = make_plan(a);
+  // (wide_a: multi-tree mode applies and has no wide form -- path A, not the plain plan)
+  if (!trees || (plan.status == BINE_ERR_UNSUPPORTED && !plan.wide_a)) plan = make_plan(a);
   if (plan.status != BINE_SUCCESS) return;
   SchedCfg cfg;
   cfg.chunk = ch;
@@ -1711,7 +1721,8 @@ constexpr int kOpNone = -1;
 // direct transport where the trees run inside its launches, through the
 // unscaled call's very form followed by one k_scale over the output on K
 static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbuf, int dtype, int op,
-                          size_t chunk_bytes, void *stream, Staging *stg = nullptr, const double *scale = nullptr) {
+                          size_t chunk_bytes, void *stream, Staging *stg = nullptr, const double *scale = nullptr,
+                          bool *wide_path_a = nullptr) {
   if (!c) return BINE_ERR_ARG;
   if (dtype < 0 || (dtype >= BINE_NUM_DTYPES && !ext_dtype(dtype))) return BINE_ERR_UNSUPPORTED;
   if (op != kOpNone) {
@@ -1734,7 +1745,12 @@ static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbu
   a.flat_ag_chunked = c->flat_ag == 2 || stg;
   a.flat_rs = c->flat_rs || stg;
   bool post_scale = false;
-  if (scale) {
+  // a wide call (wide_path_a given): `scale` is the flagged trees' multiplier
+  // (1.0 included), never a SCALE; a plan without covering trees issues
+  // nothing and says so through *wide_path_a
+  const bool wide = wide_path_a != nullptr;
+  a.wide = wide;
+  if (scale && !wide) {
     const auto *rt = dynamic_cast<const RcclTransport *>(c->tx.get());
     post_scale = rt && rt->dm_on && rt->dm && c->dm_tree &&
                  (dm_fused_supported(dtype, op) || dm_tree_supported(dtype, op, c->size));
@@ -1767,6 +1783,10 @@ static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbu
   }
   const Plan &plan = it->second.first;
   const Schedule &sc = it->second.second;
+  if (plan.wide_a) {  // nothing issued: the caller converts and runs the binary32 call
+    *wide_path_a = true;
+    return BINE_SUCCESS;
+  }
   if (plan.status != BINE_SUCCESS) return plan.status;
   hipStream_t K = (hipStream_t)stream;  // NULL = the HIP null stream, as in every HIP / RCCL API
   c->last_user = K;
@@ -1811,7 +1831,7 @@ static int run_collective(bine_comm *c, PlanArgs &a, const void *sbuf, void *rbu
     // a captured flagged tree or SCALE carries its multiplier: the scale's bits
     // are part of the graph's key
     std::string gkey = key;
-    if (a.scaled) {
+    if (a.scaled || a.wide) {
       uint64_t bits;
       memcpy(&bits, scale, sizeof bits);
       gkey += "|x" + std::to_string(bits);
@@ -2240,6 +2260,128 @@ int bine_reduce_scatter_scaled(bine_comm_t c, int algo, const void *sbuf, void *
   return run_collective(c, a, sbuf, rbuf, dtype, op, kCommChunk, stream, nullptr, &scale);
 }
 
+// ---- wide calls (bine_amd.h, "wide reductions") ------------------------------------
+
+int bine_wide_valid(int dtype, int op) {
+  return (dtype == BINE_FLOAT16 || dtype == BINE_BFLOAT16) && op >= BINE_SUM && op <= BINE_MIN ? 1 : 0;
+}
+
+int bine_widen(const void *in16, void *out32, size_t count, int dtype, void *stream) {
+  if (!bine_wide_valid(dtype, BINE_SUM)) return BINE_ERR_ARG;
+  if (count && (!in16 || !out32)) return BINE_ERR_ARG;
+  return launch_widen_h16(in16, out32, count, dtype, stream);
+}
+
+int bine_narrow(const void *in32, void *out16, size_t count, int dtype, void *stream) {
+  if (!bine_wide_valid(dtype, BINE_SUM)) return BINE_ERR_ARG;
+  if (count && (!in32 || !out16)) return BINE_ERR_ARG;
+  return launch_narrow_h16(in32, out16, count, dtype, stream);
+}
+
+int bine_reduce_tree_wide(int nleaves, const void *const *leaves, void *out, size_t count, int dtype, int op,
+                          unsigned swap, double scale, void *stream) {
+  if (!bine_wide_valid(dtype, op)) return BINE_ERR_ARG;
+  if (nleaves < 2 || nleaves > kMaxLeaves || (nleaves & (nleaves - 1))) return BINE_ERR_ARG;
+  if (!leaves || (!out && count)) return BINE_ERR_ARG;
+  return launch_reduce_tree_wide_h16(nleaves, leaves, out, count, dtype, op, stream, swap, scale);
+}
+
+// BINE_WIDE_TREES=0: every wide call takes path A.  Read at every call (the
+// tests switch it between two calls of one process).
+static bool wide_trees_on() {
+  const char *e = getenv("BINE_WIDE_TREES");
+  return !e || atoi(e) != 0;
+}
+
+// Path A: k_widen the input into the communicator's binary32 workspace, the
+// binary32 (scaled) call there -- in place when the wide call is, else into a
+// second region of the workspace -- and k_narrow its output into rbuf, all on
+// the caller's stream.  Each region starts at the 16-B phase that makes it
+// co-aligned with its 16-bit counterpart (2 x the counterpart's offset into
+// its 16-B line), so the conversions run vectorized whatever that offset is.
+static int wide_path_a(bine_comm_t c, bool rs, int algo, const void *sbuf, void *rbuf, size_t count, const int *rcounts,
+                       int dtype, int op, double scale, size_t segsize, void *stream) {
+  const bool ip = sbuf == BINE_IN_PLACE;
+  size_t n_in = count, n_out = count;
+  if (rs) {
+    n_in = 0;
+    for (int x = 0; x < c->size; x++) {
+      if (rcounts[x] < 0) return BINE_ERR_ARG;
+      n_in += (size_t)rcounts[x];
+    }
+    n_out = (size_t)rcounts[c->rank];
+  }
+  const void *src16 = ip ? rbuf : sbuf;
+  if ((n_in && !src16) || (n_out && !rbuf)) return BINE_ERR_ARG;
+  hipStream_t K = (hipStream_t)stream;
+  const size_t in_bytes = (n_in * 4 + 32 + 255) & ~(size_t)255, out_bytes = ip ? 0 : (n_out * 4 + 32 + 255) & ~(size_t)255;
+  char *ws;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (in_bytes + out_bytes > c->wide_ws_bytes) {
+      // the old workspace may still be read by enqueued work, and cached
+      // graphs of the binary32 call hold its address
+      HIP_TRY(hipStreamSynchronize(K));
+      HIP_TRY(hipStreamSynchronize(c->cstream));
+      c->drop_graphs();
+      if (c->wide_ws) HIP_TRY(hipFree(c->wide_ws));
+      c->wide_ws = nullptr;
+      c->wide_ws_bytes = 0;
+      HIP_TRY(hipMalloc(&c->wide_ws, in_bytes + out_bytes));
+      c->wide_ws_bytes = in_bytes + out_bytes;
+    }
+    ws = (char *)c->wide_ws;
+  }
+  void *win = ws + 2 * ((uintptr_t)src16 & 14);
+  void *wout = ip ? win : ws + in_bytes + 2 * ((uintptr_t)rbuf & 14);
+  int rc = launch_widen_h16(src16, win, n_in, dtype, K);
+  if (rc) return rc;
+  if (rs)
+    rc = bine_reduce_scatter_scaled(c, algo, ip ? BINE_IN_PLACE : win, wout, rcounts, BINE_FLOAT, op, scale, K);
+  else
+    rc = bine_allreduce_scaled(c, algo, ip ? BINE_IN_PLACE : win, wout, count, BINE_FLOAT, op, scale, segsize, K);
+  if (rc) return rc;
+  return launch_narrow_h16(wout, rbuf, n_out, dtype, K);
+}
+
+// the pair is checked first, on every rank alike, before any exchange and any
+// HIP call; the planner decides between path B (flagged trees in the 16-bit
+// plan) and path A
+int bine_allreduce_wide(bine_comm_t c, int algo, const void *sbuf, void *rbuf, size_t count, int dtype, int op,
+                        double scale, size_t segsize, void *stream) {
+  if (!bine_wide_valid(dtype, op)) return BINE_ERR_ARG;
+  if (algo < BINE_AR_RECURSIVEDOUBLING || algo > BINE_AR_BINE_BLOCK_BY_BLOCK_ANY_EVEN) return BINE_ERR_UNSUPPORTED;
+  if (!c) return BINE_ERR_ARG;
+  if (wide_trees_on()) {
+    PlanArgs a;
+    a.algo = algo;
+    a.count = count;
+    a.segsize = segsize;
+    size_t chunk = algo == BINE_AR_BINE_BDW_REMAP_SEGMENTED ? segsize : (segsize ? segsize : kCommChunk);
+    bool path_a = false;
+    const int rc = run_collective(c, a, sbuf, rbuf, dtype, op, chunk, stream, nullptr, &scale, &path_a);
+    if (!path_a) return rc;
+  }
+  return wide_path_a(c, false, algo, sbuf, rbuf, count, nullptr, dtype, op, scale, segsize, stream);
+}
+
+int bine_reduce_scatter_wide(bine_comm_t c, int algo, const void *sbuf, void *rbuf, const int *rcounts, int dtype,
+                             int op, double scale, void *stream) {
+  if (!bine_wide_valid(dtype, op)) return BINE_ERR_ARG;
+  if (algo < BINE_RS_RECURSIVEHALVING || algo > BINE_RS_BINE_BLOCK_BY_BLOCK_ANY_EVEN) return BINE_ERR_UNSUPPORTED;
+  if (!c || !rcounts) return BINE_ERR_ARG;
+  if (wide_trees_on()) {
+    PlanArgs a;
+    a.algo = algo;
+    a.rcounts.assign(rcounts, rcounts + c->size);
+    bool path_a = false;
+    const int rc = run_collective(c, a, sbuf, rbuf, dtype, op, kCommChunk, stream, nullptr, &scale, &path_a);
+    if (!path_a) return rc;
+  }
+  return wide_path_a(c, true, algo, sbuf, rbuf, 0, rcounts, dtype, op, scale, 0, stream);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -2442,6 +2584,34 @@ int bine_loopback_run_reduce_scatter_scaled(bine_comm_t *comms, int n, int algo,
   });
 }
 
+int bine_loopback_run_allreduce_wide(bine_comm_t *comms, int n, int algo, const void *const *sbufs,
+                                     void *const *rbufs, size_t count, int dtype, int op, double scale,
+                                     size_t segsize, int *statuses) {
+  if (!bine_wide_valid(dtype, op)) {  // before any thread, stream or HIP call
+    for (int r = 0; statuses && r < n; r++) statuses[r] = BINE_ERR_ARG;
+    return BINE_ERR_ARG;
+  }
+  return run_threads(comms, n, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_allreduce_wide(comms[r], algo, sbufs[r], rbufs[r], count, dtype, op, scale, segsize,
+                               comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_reduce_scatter_wide(bine_comm_t *comms, int n, int algo, const void *const *sbufs,
+                                          void *const *rbufs, const int *rcounts, int dtype, int op, double scale,
+                                          int *statuses) {
+  if (!bine_wide_valid(dtype, op)) {
+    for (int r = 0; statuses && r < n; r++) statuses[r] = BINE_ERR_ARG;
+    return BINE_ERR_ARG;
+  }
+  return run_threads(comms, n, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_reduce_scatter_wide(comms[r], algo, sbufs[r], rbufs[r], rcounts, dtype, op, scale,
+                                    comms[r]->stream);
+  });
+}
+
 int bine_loopback_run_reduce(bine_comm_t *comms, int n, int algo, const void *const *sbufs, void *const *rbufs,
                              size_t count, int dtype, int op, int root, int *statuses) {
   return run_threads(comms, n, statuses, [&](int r) {
@@ -2528,6 +2698,8 @@ int64_t bine_plan_schedule(int algo, int nranks, int rank, size_t count, const i
   a.flat_rs = (mode & 4) != 0;
   a.flat_ag_chunked = (mode & 8) != 0;
   a.scaled = (mode & 16) != 0;
+  a.wide = (mode & 32) != 0;
+  if (a.scaled && a.wide) return -(int64_t)BINE_ERR_ARG;
   Plan p;
   Schedule sc;
   build(a, chunk_elems(chunk_bytes, esz), relay_min_bytes, (mode & 1) != 0, p, sc);
@@ -2545,6 +2717,19 @@ int64_t bine_plan_schedule(int algo, int nranks, int rank, size_t count, const i
     workspace[3] = sc.stage_elems;
   }
   return n;
+}
+
+int bine_plan_wide(int algo, int nranks, size_t count, const int *rcounts, int mode) {
+  PlanArgs a = plan_args(algo, nranks, 0, count, rcounts, 0, 2, 0, 0);
+  a.flat_ag = (mode & 2) != 0;
+  a.flat_rs = (mode & 4) != 0;
+  a.flat_ag_chunked = (mode & 8) != 0;
+  a.wide = true;
+  Plan p;
+  Schedule sc;
+  build(a, 0, 0, (mode & 1) != 0, p, sc);
+  if (p.wide_a) return 0;
+  return p.status == BINE_SUCCESS ? 1 : -p.status;
 }
 
 // plan_dm_trees' decisions for rank `rank`'s issue schedule, with the

@@ -40,7 +40,9 @@
 // and bitwise ops only (launch_*_logic, reached from the opset-0 entry
 // points); BINE_OPSET 2 -> kernels_h16.o, the reduction kernels'
 // instantiations for the 16-bit floating types (launch_*_h16, reached the
-// same way).  Three translation units compile in parallel.
+// same way) and, for those types alone, the wide kernels k_widen / k_narrow /
+// k_reduce_tree_wide (launch_*_h16, called directly: no other compilation
+// holds a wide kernel).  Three translation units compile in parallel.
 //
 // Adding an element type: (1) a case in with_dtype, under the BINE_OPSET of
 // the compilation that is to hold it -- every reduce-family entry point, the
@@ -1114,6 +1116,379 @@ int BINE_FN(launch_scale)(const void *in, void *out, size_t count, int dtype, do
   });
 }
 #endif  // BINE_OPSET != 1
+
+#if BINE_OPSET == 2
+// ----------------------------------------------------------------------------
+// wide (binary32-accumulating) reductions of the 16-bit types (bine_amd.h,
+// "wide reductions"): k_widen / k_narrow, the conversion passes of path A, and
+// k_reduce_tree_wide, path B's tree -- the leaves stay 16-bit in memory, every
+// level of the reference's tree is one binary32 operation in registers, one
+// binary32 multiplication by (float)scale follows (by 1.0f for an unscaled
+// call: the identity on every non-NaN binary32 value, -0 and subnormals
+// included) and ONE nearest-even narrowing precedes the store.
+//
+// W8: the 8 elements of one 16-B vector as binary32, in element order.  The
+// widened leaves and the final product are pinned in VGPRs by an empty asm (no
+// instruction is emitted), so the compiler sees plain binary32 operands: it
+// can fold neither a widening into the first operation nor the product into
+// the narrowing (v_fma_mix* / v_fma_mixlo_f16; see scale1 for the -0 * 0 case
+// such a fold gets wrong).  Every level's value exists as a binary32 VGPR.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+struct W8 {
+  f32x4 a, b;  // elements 0..3, 4..7
+};
+__device__ __forceinline__ void pin(W8 &w) { asm volatile("" : "+v"(w.a), "+v"(w.b)); }
+
+template <typename T>
+__device__ __forceinline__ W8 widen16(u32x4 v) {
+  W8 w;
+  if constexpr (std::is_same_v<T, F16>) {
+    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+    f16x8 h;
+    __builtin_memcpy(&h, &v, 16);
+    const f32x8 f = __builtin_convertvector(h, f32x8);  // v_cvt_f32_f16: exact, subnormals kept
+    w.a = __builtin_shufflevector(f, f, 0, 1, 2, 3);
+    w.b = __builtin_shufflevector(f, f, 4, 5, 6, 7);
+  } else {
+    static_assert(std::is_same_v<T, BF16>, "wide types: float16, bfloat16");
+    // a bfloat16 is the upper half of a binary32: even elements by a shift, odd ones by a mask
+    const u32x4 vlo = v << 16, vhi = v & 0xffff0000u;
+    f32x4 lo, hi;
+    __builtin_memcpy(&lo, &vlo, 16);
+    __builtin_memcpy(&hi, &vhi, 16);
+    w.a = __builtin_shufflevector(lo, hi, 0, 4, 1, 5);
+    w.b = __builtin_shufflevector(lo, hi, 2, 6, 3, 7);
+  }
+  pin(w);
+  return w;
+}
+
+// round to nearest even into the 16-bit format (v_cvt_f16_f32 -- never the
+// packed round-toward-zero conversion -- resp. v_cvt_pk_bf16_f32); subnormal
+// results kept, overflow gives +-inf, NaN stays NaN
+template <typename T>
+__device__ __forceinline__ u32x4 narrow16(W8 w) {
+  pin(w);
+  const f32x8 f = __builtin_shufflevector(w.a, w.b, 0, 1, 2, 3, 4, 5, 6, 7);
+  u32x4 r;
+  if constexpr (std::is_same_v<T, F16>) {
+    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+    const f16x8 h = __builtin_convertvector(f, f16x8);
+    __builtin_memcpy(&r, &h, 16);
+  } else {
+    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+    const bf16x8 h = __builtin_convertvector(f, bf16x8);
+    __builtin_memcpy(&r, &h, 16);
+  }
+  return r;
+}
+
+template <typename T>
+__device__ __forceinline__ float widen1(T x) {
+  float f = (float)x;
+  asm volatile("" : "+v"(f));
+  return f;
+}
+template <typename T>
+__device__ __forceinline__ T narrow1(float f) {
+  asm volatile("" : "+v"(f));
+  return (T)f;
+}
+
+// one level's combine in binary32: apply<float, OP> element by element
+template <int OP>
+__device__ __forceinline__ W8 wcomb(W8 l, W8 r, bool sw) {
+  const W8 io = sw ? r : l, in = sw ? l : r;
+  W8 o;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    o.a[k] = apply<float, OP>(io.a[k], in.a[k]);
+    o.b[k] = apply<float, OP>(io.b[k], in.b[k]);
+  }
+  return o;
+}
+
+template <typename T, int OP, int NL>
+__device__ __forceinline__ T wide_scalar(const TreeArgs &t, size_t i, float m) {
+  float v[NL];
+#pragma unroll
+  for (int j = 0; j < NL; j++) v[j] = widen1<T>(((const T *)t.leaf[j])[i]);
+  int lvl = 0;
+#pragma unroll
+  for (int w = 1; w < NL; w <<= 1, lvl++)
+#pragma unroll
+    for (int j = 0; j < NL; j += 2 * w) v[j] = comb<float, OP>(v[j], v[j + w], (t.swap >> lvl) & 1);
+  return narrow1<T>(v[0] * m);
+}
+
+// tree_tile's shape -- the same loads (position 0 plain, the others
+// non-temporal), groups of G = min(NL, 8) leaves forming complete subtrees,
+// U vectors of each leaf per lane in flight, non-temporal stores -- with
+// every vector widened as it is consumed: the loads stay 16-B vectors of
+// 16-bit elements, only the values being combined are binary32.
+template <typename T, int OP, int NL, int U, bool GUARD>
+__device__ __forceinline__ void wide_tile(const u32x4 *const *lp, u32x4 *vo, size_t base, size_t nvec, unsigned swap,
+                                          float m) {
+  constexpr int G = NL < 8 ? NL : 8, NG = NL / G, LG = G == 2 ? 1 : G == 4 ? 2 : 3;
+  W8 part[U][NG];
+#pragma unroll
+  for (int g = 0; g < NG; g++) {
+    u32x4 v[U][G];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if (!GUARD || i < nvec) {
+        if (g == 0) v[u][0] = lp[0][i];
+#pragma unroll
+        for (int j = g == 0 ? 1 : 0; j < G; j++) v[u][j] = __builtin_nontemporal_load(lp[g * G + j] + i);
+      } else {
+#pragma unroll
+        for (int j = 0; j < G; j++) v[u][j] = u32x4{0, 0, 0, 0};
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      W8 x[G];
+#pragma unroll
+      for (int j = 0; j < G; j++) x[j] = widen16<T>(v[u][j]);
+      int lvl = 0;
+#pragma unroll
+      for (int w = 1; w < G; w <<= 1, lvl++)
+#pragma unroll
+        for (int j = 0; j < G; j += 2 * w) x[j] = wcomb<OP>(x[j], x[j + w], (swap >> lvl) & 1);
+      part[u][g] = x[0];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    int lvl = LG;
+#pragma unroll
+    for (int w = 1; w < NG; w <<= 1, lvl++)
+#pragma unroll
+      for (int g = 0; g < NG; g += 2 * w) part[u][g] = wcomb<OP>(part[u][g], part[u][g + w], (swap >> lvl) & 1);
+    W8 p;
+    p.a = part[u][0].a * m;
+    p.b = part[u][0].b * m;
+    const size_t i = base + (size_t)u * kBlock;
+    if (!GUARD || i < nvec) __builtin_nontemporal_store(narrow16<T>(p), vo + i);
+  }
+}
+
+template <typename T, int OP, int NL>
+__global__ __launch_bounds__(kBlock) void k_reduce_tree_wide_edges(TreeArgs t, float m) {
+  constexpr size_t V = 16 / sizeof(T);
+  T *out = (T *)t.out;
+  for (size_t i = threadIdx.x; i < t.head; i += kBlock) out[i] = wide_scalar<T, OP, NL>(t, i, m);
+  for (size_t i = t.head + t.nvec * V + threadIdx.x; i < t.n; i += kBlock) out[i] = wide_scalar<T, OP, NL>(t, i, m);
+}
+
+template <typename T, int OP, int NL, int U>
+__global__ __launch_bounds__(kBlock) void k_reduce_tree_wide(TreeArgs t, float m) {
+  T *out = (T *)t.out;
+  const u32x4 *lp[NL];
+#pragma unroll
+  for (int j = 0; j < NL; j++) lp[j] = reinterpret_cast<const u32x4 *>((const T *)t.leaf[j] + t.head);
+  u32x4 *vo = reinterpret_cast<u32x4 *>(out + t.head);
+  const size_t base = (size_t)blockIdx.x * kBlock * U + threadIdx.x;
+  if ((size_t)(blockIdx.x + 1) * kBlock * U <= t.nvec) wide_tile<T, OP, NL, U, false>(lp, vo, base, t.nvec, t.swap, m);
+  else wide_tile<T, OP, NL, U, true>(lp, vo, base, t.nvec, t.swap, m);
+}
+
+template <typename T, int OP, int NL>
+__global__ __launch_bounds__(kBlock) void k_reduce_tree_wide_scalar(TreeArgs t, float m) {
+  T *out = (T *)t.out;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < t.n; i += (size_t)gridDim.x * kBlock)
+    out[i] = wide_scalar<T, OP, NL>(t, i, m);
+}
+
+// vectors of each leaf per lane in flight: k_reduce_tree's, halved where the
+// binary32 intermediates would otherwise cost a wave of occupancy (DESIGN.md,
+// "wide reductions": the register budget)
+template <int NL>
+constexpr int kWideU = NL == 2 ? 8 : NL == 4 ? 4 : NL == 8 ? 2 : 1;
+
+template <typename T, int OP, int NL>
+static hipError_t wide_launch(const TreeArgs &t, hipStream_t st, float m) {
+  constexpr int U = kWideU<NL>;
+  constexpr size_t V = 16 / sizeof(T);
+  const dim3 blk(kBlock);
+  if (t.vec) {
+    const dim3 tiles((unsigned)((t.nvec + (size_t)kBlock * U - 1) / ((size_t)kBlock * U)));
+    if (tiles.x) hipLaunchKernelGGL((k_reduce_tree_wide<T, OP, NL, U>), tiles, blk, 0, st, t, m);
+    if (t.head || t.head + t.nvec * V < t.n)
+      hipLaunchKernelGGL((k_reduce_tree_wide_edges<T, OP, NL>), dim3(1), blk, 0, st, t, m);
+  } else {
+    hipLaunchKernelGGL((k_reduce_tree_wide_scalar<T, OP, NL>), dim3(scalar_blocks(t.n)), blk, 0, st, t, m);
+  }
+  return hipGetLastError();
+}
+
+int launch_reduce_tree_wide_h16(int nl, const void *const *leaf, void *out, size_t count, int dtype, int op,
+                                void *stream, unsigned swap, double scale) {
+  if (!bine_wide_valid(dtype, op)) return BINE_ERR_ARG;
+  if (nl < 2 || nl > kMaxLeaves || (nl & (nl - 1))) return BINE_ERR_ARG;
+  if (count == 0) return BINE_SUCCESS;
+  TreeArgs t{};
+  for (int j = 0; j < nl; j++) t.leaf[j] = leaf[j];
+  t.out = out;
+  t.n = count;
+  t.swap = swap;
+  const uintptr_t oo = (uintptr_t)out;
+  bool co = (oo % 2) == 0;
+  for (int j = 0; j < nl; j++) co = co && (((uintptr_t)leaf[j] ^ oo) & 15) == 0;
+  const VecSplit vs = co ? vec_split(oo, count, 2) : VecSplit{count, 0};
+  t.vec = co ? 1 : 0;
+  t.head = vs.head;
+  t.nvec = vs.nvec;
+  const float m = (float)scale;  // round to nearest even
+  hipStream_t st = (hipStream_t)stream;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return status(with_op<T>(op, [&](auto opc) {
+      return with_nl(nl, [&](auto nlc) { return wide_launch<T, decltype(opc)::value, decltype(nlc)::value>(t, st, m); });
+    }));
+  });
+}
+
+// ----------------------------------------------------------------------------
+// k_widen: out32[i] = in16[i] widened exactly; k_narrow: out16[i] = in32[i]
+// rounded to nearest even.  One 16-B vector of 16-bit elements faces two of
+// binary32; one tile of kBlock * kWnU 16-bit vectors per workgroup, every load
+// issued before the first store.  The elements before the first 16-B boundary
+// of the 16-bit operand and after its last whole vector go scalar through
+// workgroup 0; operands whose 16-B boundaries do not coincide take the scalar
+// grid-stride kernels.  The source is read once: non-temporal loads.  k_widen
+// stores plainly (the collective that follows reads the workspace), k_narrow
+// non-temporally, as k_scale and the trees store their results.
+constexpr int kWnU = 4;
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_widen(const T *in, float *out, size_t head, size_t nvec, size_t n) {
+  if (blockIdx.x == 0) {
+    for (size_t i = threadIdx.x; i < head; i += kBlock) out[i] = widen1<T>(in[i]);
+    for (size_t i = head + nvec * 8 + threadIdx.x; i < n; i += kBlock) out[i] = widen1<T>(in[i]);
+  }
+  const u32x4 *vs = reinterpret_cast<const u32x4 *>(in + head);
+  f32x4 *vd = reinterpret_cast<f32x4 *>(out + head);
+  const size_t base = (size_t)blockIdx.x * kBlock * kWnU + threadIdx.x;
+  if (base + (kWnU - 1) * (size_t)kBlock < nvec) {
+    u32x4 x[kWnU];
+#pragma unroll
+    for (int u = 0; u < kWnU; u++) x[u] = __builtin_nontemporal_load(vs + base + (size_t)u * kBlock);
+#pragma unroll
+    for (int u = 0; u < kWnU; u++) {
+      const W8 w = widen16<T>(x[u]);
+      const size_t i = base + (size_t)u * kBlock;
+      vd[2 * i] = w.a;
+      vd[2 * i + 1] = w.b;
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < kWnU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if (i < nvec) {
+        const W8 w = widen16<T>(vs[i]);
+        vd[2 * i] = w.a;
+        vd[2 * i + 1] = w.b;
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_narrow(const float *in, T *out, size_t head, size_t nvec, size_t n) {
+  if (blockIdx.x == 0) {
+    for (size_t i = threadIdx.x; i < head; i += kBlock) out[i] = narrow1<T>(in[i]);
+    for (size_t i = head + nvec * 8 + threadIdx.x; i < n; i += kBlock) out[i] = narrow1<T>(in[i]);
+  }
+  const f32x4 *vs = reinterpret_cast<const f32x4 *>(in + head);
+  u32x4 *vd = reinterpret_cast<u32x4 *>(out + head);
+  const size_t base = (size_t)blockIdx.x * kBlock * kWnU + threadIdx.x;
+  if (base + (kWnU - 1) * (size_t)kBlock < nvec) {
+    W8 x[kWnU];
+#pragma unroll
+    for (int u = 0; u < kWnU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      x[u].a = __builtin_nontemporal_load(vs + 2 * i);
+      x[u].b = __builtin_nontemporal_load(vs + 2 * i + 1);
+    }
+#pragma unroll
+    for (int u = 0; u < kWnU; u++) __builtin_nontemporal_store(narrow16<T>(x[u]), vd + base + (size_t)u * kBlock);
+  } else {
+#pragma unroll
+    for (int u = 0; u < kWnU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if (i < nvec) {
+        W8 w;
+        w.a = vs[2 * i];
+        w.b = vs[2 * i + 1];
+        vd[i] = narrow16<T>(w);
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_widen_scalar(const T *in, float *out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
+    out[i] = widen1<T>(in[i]);
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_narrow_scalar(const float *in, T *out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
+    out[i] = narrow1<T>(in[i]);
+}
+
+// the split of n elements at (p16, p32): `head` elements up to the first 16-B
+// boundary of the 16-bit operand, where the binary32 operand must stand on a
+// 16-B boundary too; false: the boundaries do not coincide (all scalar)
+static bool wn_split(uintptr_t p16, uintptr_t p32, size_t n, VecSplit *vs) {
+  if (p16 % 2 || p32 % 4) return false;
+  const size_t head = ((16 - (p16 & 15)) & 15) / 2;
+  if ((p32 + 4 * head) & 15) return false;
+  *vs = {std::min(head, n), (n - std::min(head, n)) / 8};
+  return true;
+}
+static unsigned wn_blocks(size_t nvec) {
+  const size_t tiles = (nvec + (size_t)kBlock * kWnU - 1) / ((size_t)kBlock * kWnU);
+  return (unsigned)(tiles ? tiles : 1);
+}
+
+int launch_widen_h16(const void *in16, void *out32, size_t count, int dtype, void *stream) {
+  if (!bine_wide_valid(dtype, BINE_SUM)) return BINE_ERR_ARG;
+  if (count == 0) return BINE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    VecSplit vs;
+    if (wn_split((uintptr_t)in16, (uintptr_t)out32, count, &vs))
+      hipLaunchKernelGGL((k_widen<T>), dim3(wn_blocks(vs.nvec)), dim3(kBlock), 0, st, (const T *)in16, (float *)out32,
+                         vs.head, vs.nvec, count);
+    else
+      hipLaunchKernelGGL((k_widen_scalar<T>), dim3(scalar_blocks(count)), dim3(kBlock), 0, st, (const T *)in16,
+                         (float *)out32, count);
+    return status(hipGetLastError());
+  });
+}
+
+int launch_narrow_h16(const void *in32, void *out16, size_t count, int dtype, void *stream) {
+  if (!bine_wide_valid(dtype, BINE_SUM)) return BINE_ERR_ARG;
+  if (count == 0) return BINE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    VecSplit vs;
+    if (wn_split((uintptr_t)out16, (uintptr_t)in32, count, &vs))
+      hipLaunchKernelGGL((k_narrow<T>), dim3(wn_blocks(vs.nvec)), dim3(kBlock), 0, st, (const float *)in32, (T *)out16,
+                         vs.head, vs.nvec, count);
+    else
+      hipLaunchKernelGGL((k_narrow_scalar<T>), dim3(scalar_blocks(count)), dim3(kBlock), 0, st, (const float *)in32,
+                         (T *)out16, count);
+    return status(hipGetLastError());
+  });
+}
+#endif  // BINE_OPSET == 2
 
 #if BINE_OPSET == 0
 // ----------------------------------------------------------------------------

@@ -313,9 +313,10 @@ bool flat_rs(Builder &b, const PlanArgs &a, int src, const std::vector<uint64_t>
     // scaled call: this tree's output is a final value of the collective (every
     // allreduce / reduce-scatter caller of flat_rs only moves it afterwards),
     // so the tree scales it; make_plan then appends no trailing SCALE
-    if (a.scaled && cl) b.p.prims.back().flags |= BINE_PRIM_SCALED;
+    // (a wide call: the same trees, flagged BINE_PRIM_WIDE instead)
+    if ((a.scaled || a.wide) && cl) b.p.prims.back().flags |= a.wide ? BINE_PRIM_WIDE : BINE_PRIM_SCALED;
   }
-  if (a.scaled) b.p.scale_fused = true;
+  if (a.scaled || a.wide) b.p.scale_fused = true;
   if (agc && k > 0) flat_ag_chunk(b, a, boff, bcnt, (k - 1) * ch, ch);
   return agc;
 }
@@ -2217,14 +2218,25 @@ static Plan make_plan_unscaled(const PlanArgs &a);
 Plan make_plan(const PlanArgs &a) {
   const bool ar = a.algo >= BINE_AR_RECURSIVEDOUBLING && a.algo <= BINE_AR_BINE_BLOCK_BY_BLOCK_ANY_EVEN;
   const bool rs = a.algo >= BINE_RS_RECURSIVEHALVING && a.algo <= BINE_RS_BINE_BLOCK_BY_BLOCK_ANY_EVEN;
-  if (a.scaled && !ar && !rs) {
+  if ((a.scaled || a.wide) && !ar && !rs) {
     Plan p;
     p.status = BINE_ERR_UNSUPPORTED;
     return p;
   }
   Plan p = make_plan_unscaled(a);
   if (a.scaled) append_scale(p, a);
+  if (a.wide) wide_or_path_a(p);
   return p;
+}
+
+// a wide call's plan: one whose flagged trees cover the output (path B), or
+// no plan at all -- BINE_ERR_UNSUPPORTED with Plan::wide_a set, the caller
+// takes path A; an error status stays what it is
+void wide_or_path_a(Plan &p) {
+  if (p.status != BINE_SUCCESS || p.scale_fused) return;
+  p.prims.clear();
+  p.status = BINE_ERR_UNSUPPORTED;
+  p.wide_a = true;
 }
 
 // (with a.scaled: the flat reduce-scatter's trees flagged, Plan::scale_fused

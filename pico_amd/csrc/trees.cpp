@@ -124,6 +124,7 @@ Plan make_tree_plan(const PlanArgs &a) {
     b.flat_ag = false;  // instances keep their own (mirrored) allgather
     b.flat_rs = false;  // and their own halving steps
     b.scaled = false;   // a scaled call: one trailing SCALE over the whole output, below
+    b.wide = false;     // a wide call: no covering trees here, path A (below)
     b.rank = v;
     Mapper m;
     if (allreduce) {
@@ -191,6 +192,7 @@ Plan make_tree_plan(const PlanArgs &a) {
     if (any) gid++;
   }
   if (a.scaled) append_scale(out, a);
+  if (a.wide) wide_or_path_a(out);
   return out;
 }
 
