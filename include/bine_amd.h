@@ -307,6 +307,31 @@ int bine_reduce_tree_wide(int nleaves, const void *const *leaves, void *out, siz
  * e.g. allreduce_bine_bdw_remap, libbine_allreduce.c:849-852): dst[0:bytes) =
  * src[0:bytes), stream-ordered, the kernel every COPY primitive runs. */
 int bine_copy(void *dst, const void *src, size_t bytes, void *stream);
+/* n independent device copies, dsts[k][0:bytes[k]) = srcs[k][0:bytes[k]) for
+ * every k, stream-ordered, in ceil(nonempty / BINE_COPY_SEGS_PER_LAUNCH)
+ * launches of k_copy_segs (the segment descriptors travel by value in the
+ * kernel arguments: nothing is uploaded, nothing is synchronized, and the
+ * caller's arrays may be reused as soon as the call returns).  A segment with
+ * bytes[k] == 0 is skipped and its pointers may be NULL; n == 0 or every
+ * segment empty is success without a launch.  Any alignment: a segment whose
+ * source is not co-aligned with its destination mod 16 B is copied in the
+ * same launch (aligned loads, shifted in registers).  The destination ranges
+ * must not overlap each other or any source range; otherwise the result is
+ * undefined.  BINE_ERR_ARG: n < 0, n > BINE_MULTI_MAX, a NULL array with
+ * n > 0, a NULL pointer with a non-zero size. */
+#define BINE_MULTI_MAX 1024
+#define BINE_COPY_SEGS_PER_LAUNCH 128
+int bine_copy_segments(int n, void *const *dsts, const void *const *srcs, const size_t *bytes, void *stream);
+/* The tile table of that call (host only; the launcher walks the same table):
+ * 5 words per tile into out (up to cap tiles) -- (launch, segment, byte offset
+ * in the segment, bytes, kind).  Kind 0 = a vector tile, one workgroup's up
+ * to 2048 16-B vectors, starting and ending on 16-B boundaries of the
+ * destination; kind 1 = the fewer than 16 bytes before the destination's
+ * first 16-B boundary or after its last full vector, copied byte-wise by the
+ * segment's first workgroup.  Empty segments have no tile.  Returns the
+ * number of tiles (may exceed cap) or -status. */
+int64_t bine_plan_segments(int n, const uint64_t *dst_addr, const uint64_t *src_addr, const size_t *bytes,
+                           uint64_t *out, int64_t cap);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -631,6 +656,44 @@ int bine_allreduce_wide(bine_comm_t comm, int algo, const void *sbuf, void *rbuf
                         int dtype, int op, double scale, size_t segsize, void *stream);
 int bine_reduce_scatter_wide(bine_comm_t comm, int algo, const void *sbuf, void *rbuf,
                              const int *rcounts, int dtype, int op, double scale, void *stream);
+/* ---- multi-buffer allreduce: n tensors reduced as one collective ------------
+ * Let C be the element-wise concatenation of the n input segments in order,
+ * count = sum of counts[k].  The call leaves in rbufs[k] the k-th slice
+ * (counts[k] elements) of the result of ONE single-buffer call on C with
+ * sbuf = BINE_IN_PLACE and the same algorithm, `segsize` and communicator
+ * settings, bit for bit (but for the unspecified NaN payload of the 16-bit
+ * types' contract):
+ *   wide == 0, scale == 1.0   bine_allreduce         every pair bine_op_valid accepts
+ *   wide == 0, scale != 1.0   bine_allreduce_scaled  bine_scale_valid
+ *   wide != 0, any scale      bine_allreduce_wide    bine_wide_valid
+ * sbufs == NULL, sbufs[k] == rbufs[k] or sbufs[k] == BINE_IN_PLACE: segment k
+ * is in place (its input is rbufs[k]).  A segment with counts[k] == 0 is
+ * skipped and its pointers may be NULL.  Every rank passes the same n and
+ * counts.  The rbufs ranges must not overlap each other or any input range
+ * of another segment.
+ * Mechanism: bine_copy_segments packs the inputs contiguously into a
+ * workspace the communicator owns (its own, not the wide calls'; grown like
+ * theirs: both streams synchronized, cached graphs dropped, reallocated --
+ * only when a call needs more than any call before), the single call runs
+ * there in place, bine_copy_segments unpacks into rbufs; all on the caller's
+ * stream, without host synchronization in steady state.  The packed region
+ * starts at the 16-B phase of the first non-empty input, so 16-B aligned
+ * tensors of sizes that are multiples of 16 B are packed and unpacked on the
+ * co-aligned path throughout.  Pack and unpack are ordinary launches, never
+ * captured; with graph mode on the inner call is captured and replayed as
+ * any call on that address.  A call with exactly one non-empty segment is the
+ * single call on the caller's own buffers.  n == 0 or count == 0: success,
+ * nothing is written.
+ * BINE_ERR_ARG, on every rank alike, before any exchange and any HIP call, in
+ * this order: a (dtype, op) pair the selected family refuses (checked before
+ * `comm` is looked at); n < 0 or n > BINE_MULTI_MAX; counts == NULL or
+ * rbufs == NULL with n > 0; a NULL buffer with a non-zero count.  Then an
+ * algorithm id outside the allreduce range is BINE_ERR_UNSUPPORTED as in
+ * bine_allreduce, and comm == NULL is BINE_ERR_ARG.  Not provided: a
+ * reduce-scatter / allgather / rooted form, mixed element types. */
+int bine_allreduce_multi(bine_comm_t comm, int algo, int n, const void *const *sbufs, void *const *rbufs,
+                         const size_t *counts, int dtype, int op, double scale, int wide, size_t segsize,
+                         void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -704,6 +767,12 @@ int bine_loopback_run_reduce_scatter_wide(bine_comm_t *comms, int nranks, int al
                                           const void *const *sbufs, void *const *rbufs,
                                           const int *rcounts, int dtype, int op, double scale,
                                           int *statuses);
+/* sbufs (NULL: every segment in place) and rbufs hold nranks * n pointers,
+ * rank r's segment k at [r * n + k] */
+int bine_loopback_run_allreduce_multi(bine_comm_t *comms, int nranks, int algo, int n,
+                                      const void *const *sbufs, void *const *rbufs, const size_t *counts,
+                                      int dtype, int op, double scale, int wide, size_t segsize,
+                                      int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

@@ -23,6 +23,12 @@ buffers with every pairwise operation in binary32 and ONE rounding to 16 bits
 per output element: exactly the float32 call's result on the widened inputs,
 rounded to nearest even.  ``wide_plan`` says which of the two bit-identical
 paths a call takes.
+
+Multi-buffer allreduce: ``allreduce_multi(algo, sbufs, rbufs, ...)`` reduces a
+list of tensors as ONE collective -- the slices of the single call on their
+concatenation, bit for bit (plain, ``scale=`` / ``op="avg"``, ``wide=True``).
+``copy_segments`` is the many-ranges-one-launch device copy that packs and
+unpacks them.
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

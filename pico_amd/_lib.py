@@ -56,6 +56,10 @@ ALGOS = {
 }
 IN_PLACE = ctypes.c_void_p(-1 & 0xFFFFFFFFFFFFFFFF)
 UNIQUE_ID_BYTES = 128
+# bine_copy_segments / bine_allreduce_multi: segments per call (BINE_MULTI_MAX) and
+# per launch of k_copy_segs (BINE_COPY_SEGS_PER_LAUNCH)
+MULTI_MAX = 1024
+COPY_SEGS_PER_LAUNCH = 128
 
 
 class Prim(ctypes.Structure):
@@ -167,6 +171,10 @@ def lib():
         "bine_loopback_run_allreduce_wide": ([vp, i, i, vp, vp, sz, i, i, ctypes.c_double, sz, vp], i),
         "bine_loopback_run_reduce_scatter_wide": ([vp, i, i, vp, vp, vp, i, i, ctypes.c_double, vp], i),
         "bine_plan_wide": ([i, i, sz, vp, i], i),
+        "bine_copy_segments": ([i, vp, vp, vp, vp], i),
+        "bine_plan_segments": ([i, vp, vp, vp, vp, ctypes.c_int64], ctypes.c_int64),
+        "bine_allreduce_multi": ([vp, i, i, vp, vp, vp, i, i, ctypes.c_double, i, sz, vp], i),
+        "bine_loopback_run_allreduce_multi": ([vp, i, i, i, vp, vp, vp, i, i, ctypes.c_double, i, sz, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

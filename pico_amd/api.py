@@ -454,6 +454,88 @@ def wide_plan(coll: str, algo, nranks: int, count: int = 0, rcounts=None, trees:
     return bool(r)
 
 
+# ---- multi-buffer forms: many tensors, one call ------------------------------------
+
+def copy_segments(dsts, srcs, nbytes: Sequence[int], stream=None) -> None:
+    """dsts[k][:nbytes[k]] = srcs[k][:nbytes[k]] for every k (bytes), all in
+    ceil(non-empty / COPY_SEGS_PER_LAUNCH) launches of k_copy_segs
+    (bine_copy_segments).  Any alignment; empty segments may be None; the
+    destination ranges must not overlap each other or any source range."""
+    n = len(nbytes)
+    if len(dsts) != n or len(srcs) != n:
+        raise ValueError("copy_segments: dsts, srcs and nbytes differ in length")
+    check(lib().bine_copy_segments(n, _ptrs(dsts), _ptrs(srcs), (ctypes.c_size_t * max(n, 1))(*nbytes),
+                                   _stream(stream, None)), "bine_copy_segments")
+
+
+def plan_segments(dst_addrs: Sequence[int], src_addrs: Sequence[int], nbytes: Sequence[int]):
+    """The tile table of that call (bine_plan_segments, host only): a list of
+    (launch, segment, byte offset in the segment, bytes, kind), kind 0 = a
+    vector tile, 1 = head / tail bytes."""
+    n = len(nbytes)
+    d = (ctypes.c_uint64 * max(n, 1))(*dst_addrs)
+    s = (ctypes.c_uint64 * max(n, 1))(*src_addrs)
+    b = (ctypes.c_size_t * max(n, 1))(*nbytes)
+    nt = lib().bine_plan_segments(n, d, s, b, None, 0)
+    if nt < 0:
+        raise BineError(int(-nt), "bine_plan_segments")
+    out = (ctypes.c_uint64 * max(5 * int(nt), 1))()
+    lib().bine_plan_segments(n, d, s, b, out, nt)
+    return [tuple(int(x) for x in out[5 * k:5 * k + 5]) for k in range(int(nt))]
+
+
+def _multi_counts(rbufs, counts):
+    if counts is None:
+        counts = [b.numel() for b in rbufs]
+    if len(counts) != len(rbufs):
+        raise ValueError("allreduce_multi: counts and rbufs differ in length")
+    return (ctypes.c_size_t * max(len(counts), 1))(*counts)
+
+
+def _multi_family(op: str, scale, wide: bool, comm: Comm):
+    """(op, the C call's scale): op="avg" through _scaled; no scale = 1.0, the
+    unscaled call (wide=False) or the wide call times one"""
+    op, scale = _scaled(op, scale, comm)
+    return op, 1.0 if scale is None else float(scale)
+
+
+def allreduce_multi(algo, sbufs, rbufs, dtype, op: str, comm: Comm, counts=None, segsize: int = 0, stream=None,
+                    scale=None, wide: bool = False) -> None:
+    """bine_allreduce_multi: the tensors of `rbufs` receive the slices of ONE
+    allreduce over the concatenation of `sbufs`, bit for bit what allreduce /
+    allreduce (scale=) / allreduce_wide (wide=True) gives in place on
+    torch.cat(sbufs).  sbufs=None: every tensor in place; sbufs[k] is
+    rbufs[k] or IN_PLACE: tensor k in place.  counts (elements, the same on
+    every rank) defaults to each rbuf's numel()."""
+    if sbufs is not None and len(sbufs) != len(rbufs):
+        raise ValueError("allreduce_multi: sbufs and rbufs differ in length")
+    op, scale = _multi_family(op, scale, wide, comm)
+    c = _multi_counts(rbufs, counts)
+    check(lib().bine_allreduce_multi(comm.handle, _algo("allreduce", algo), len(rbufs),
+                                     None if sbufs is None else _ptrs(sbufs), _ptrs(rbufs), c,
+                                     _dtype(dtype, *rbufs), OPS[op], scale, int(bool(wide)), segsize,
+                                     _stream(stream, comm)), f"allreduce_{algo} (multi)")
+
+
+def loopback_allreduce_multi(comms, algo, sbufs, rbufs, dtype, op="sum", counts=None, segsize=0, scale=None,
+                             wide=False):
+    """sbufs (None: in place) / rbufs: one list of tensors per virtual rank.
+    Returns (status, per-rank statuses)."""
+    st = (ctypes.c_int * len(comms))()
+    hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
+    op, scale = _multi_family(op, scale, wide, comms[0])
+    n = len(rbufs[0])
+    if any(len(r) != n for r in rbufs) or (sbufs is not None and any(len(s) != n for s in sbufs)):
+        raise ValueError("loopback_allreduce_multi: the ranks' lists differ in length")
+    c = _multi_counts(rbufs[0], counts)
+    flat_r = [b for r in rbufs for b in r]
+    flat_s = None if sbufs is None else _ptrs([b for s in sbufs for b in s])
+    rc = lib().bine_loopback_run_allreduce_multi(hs, len(comms), _algo("allreduce", algo), n, flat_s,
+                                                 _ptrs(flat_r), c, _dtype(dtype, *flat_r), OPS[op], scale,
+                                                 int(bool(wide)), segsize, st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -841,7 +923,7 @@ globals().update(ENTRY_POINTS)
 __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fused_msgs", "reduce_local", "reduce3", "fill_pico", "checksum", "copy",
            "rccl_version", "scale", "scale_valid", "wide_valid", "widen", "narrow", "reduce_tree_wide",
            "allreduce_wide", "reduce_scatter_wide", "loopback_allreduce_wide", "loopback_reduce_scatter_wide",
-           "wide_plan",
+           "wide_plan", "copy_segments", "plan_segments", "allreduce_multi", "loopback_allreduce_multi",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

@@ -199,6 +199,27 @@ int launch_reduce_tree_wide_h16(int nl, const void *const *leaf, void *out, size
 // copy_buffer on the device (k_copy); hipMemcpyAsync when src / dst are not
 // co-aligned mod 16 B
 int launch_copy(void *dst, const void *src, size_t bytes, void *stream);
+// segmented copy (bine_copy_segments): the launches of one call, built by the
+// host-only plan_seg_launches (segments.cpp) and issued as k_copy_segs by
+// launch_copy_segments.  A launch carries up to kSegsPerLaunch non-empty
+// segments by value; its grid is the concatenation of their workgroups, one
+// per tile of kCopyTileVecs 16-B vectors (k_copy's tile), at least one per
+// segment; the first workgroup of a segment also copies its head / tail bytes.
+constexpr int kSegsPerLaunch = BINE_COPY_SEGS_PER_LAUNCH;
+constexpr uint64_t kCopyTileVecs = 2048;           // kBlock * kCopyU (kernels.hip asserts it)
+constexpr uint64_t kSegMaxWgs = (1u << 24) - 1;    // workgroups of one launch (256 lanes each: below 2^32 lanes)
+struct SegLaunch {
+  int nseg = 0;
+  int seg[kSegsPerLaunch];             // the caller's segment index per slot
+  uint64_t head[kSegsPerLaunch];       // bytes before the destination's first 16-B boundary
+  uint64_t nvec[kSegsPerLaunch];       // full 16-B vectors after them
+  uint32_t tile0[kSegsPerLaunch + 1];  // first workgroup per slot; [nseg] = the grid
+};
+// BINE_SUCCESS, or BINE_ERR_ARG (n out of range, a NULL array, a zero address
+// with a non-zero size, more than kSegMaxWgs workgroups in one launch)
+int plan_seg_launches(int n, const uint64_t *dst_addr, const uint64_t *src_addr, const size_t *bytes,
+                      std::vector<SegLaunch> &out);
+int launch_copy_segments(int n, void *const *dsts, const void *const *srcs, const size_t *bytes, void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -526,6 +526,10 @@ struct bine_comm {
   // like tmp[], reused across calls
   void *wide_ws = nullptr;
   size_t wide_ws_bytes = 0;
+  // packed buffer of bine_allreduce_multi; its own, since the inner call may
+  // be a wide one using wide_ws; grown and reused the same way
+  void *multi_ws = nullptr;
+  size_t multi_ws_bytes = 0;
   struct OpTime { hipEvent_t a = nullptr, b = nullptr; int xchg = 0, nprims = 0; uint64_t bytes = 0; };
   std::vector<OpTime> prof;
   size_t prof_n = 0;
@@ -548,6 +552,7 @@ struct bine_comm {
     for (int t = 0; t < 4; t++)
       if (tmp[t]) (void)hipFree(tmp[t]);
     if (wide_ws) (void)hipFree(wide_ws);
+    if (multi_ws) (void)hipFree(multi_ws);
     for (auto e : ev) (void)hipEventDestroy(e);
     if (order_ev) (void)hipEventDestroy(order_ev);
     for (auto &p : prof) {
@@ -2035,6 +2040,10 @@ int bine_copy(void *dst, const void *src, size_t bytes, void *stream) {
   return launch_copy(dst, src, bytes, stream);
 }
 
+int bine_copy_segments(int n, void *const *dsts, const void *const *srcs, const size_t *bytes, void *stream) {
+  return launch_copy_segments(n, dsts, srcs, bytes, stream);  // its planner checks the arguments
+}
+
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream) {
   return launch_fill_pico(buf, count, dtype, seed, stream);
 }
@@ -2382,6 +2391,94 @@ int bine_reduce_scatter_wide(bine_comm_t c, int algo, const void *sbuf, void *rb
   return wide_path_a(c, true, algo, sbuf, rbuf, 0, rcounts, dtype, op, scale, 0, stream);
 }
 
+// ---- multi-buffer allreduce (bine_amd.h, "multi-buffer allreduce") -------------------
+
+// the single call a multi call stands for
+static int multi_single(bine_comm_t c, int algo, const void *sbuf, void *rbuf, size_t count, int dtype, int op,
+                        double scale, int wide, size_t segsize, void *stream) {
+  if (wide) return bine_allreduce_wide(c, algo, sbuf, rbuf, count, dtype, op, scale, segsize, stream);
+  if (scale != 1.0) return bine_allreduce_scaled(c, algo, sbuf, rbuf, count, dtype, op, scale, segsize, stream);
+  return bine_allreduce(c, algo, sbuf, rbuf, count, dtype, op, segsize, stream);
+}
+
+// the checks that need no communicator, in the header's order; sb(k) = segment
+// k's input (NULL: none given)
+static int multi_args(int algo, int n, const void *const *sbufs, void *const *rbufs, const size_t *counts, int dtype,
+                      int op, double scale, int wide) {
+  const int ok = wide ? bine_wide_valid(dtype, op) : scale != 1.0 ? bine_scale_valid(dtype, op)
+                                                                  : bine_op_valid(dtype, op);
+  if (!ok) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX) return BINE_ERR_ARG;
+  if (n > 0 && (!counts || !rbufs)) return BINE_ERR_ARG;
+  for (int k = 0; k < n; k++)
+    if (counts[k] && (!rbufs[k] || (sbufs && !sbufs[k]))) return BINE_ERR_ARG;
+  if (algo < BINE_AR_RECURSIVEDOUBLING || algo > BINE_AR_BINE_BLOCK_BY_BLOCK_ANY_EVEN) return BINE_ERR_UNSUPPORTED;
+  return BINE_SUCCESS;
+}
+
+// Pack (bine_copy_segments) into the communicator's workspace, the single
+// call there in place, unpack into rbufs: wide_path_a's pattern, all on the
+// caller's stream.  The packed region starts at the first non-empty input's
+// offset into its 16-B line, so equally aligned tensors stay co-aligned.
+int bine_allreduce_multi(bine_comm_t c, int algo, int n, const void *const *sbufs, void *const *rbufs,
+                         const size_t *counts, int dtype, int op, double scale, int wide, size_t segsize,
+                         void *stream) {
+  if (const int rc = multi_args(algo, n, sbufs, rbufs, counts, dtype, op, scale, wide)) return rc;
+  if (!c) return BINE_ERR_ARG;
+  const size_t esz = bine_dtype_size(dtype);
+  auto input = [&](int k) -> const void * {
+    return !sbufs || sbufs[k] == BINE_IN_PLACE || sbufs[k] == rbufs[k] ? rbufs[k] : sbufs[k];
+  };
+  size_t total = 0;
+  int nonempty = 0, first = -1;
+  for (int k = 0; k < n; k++) {
+    if (!counts[k]) continue;
+    if (first < 0) first = k;
+    nonempty++;
+    total += counts[k];
+  }
+  if (nonempty == 0) return BINE_SUCCESS;
+  if (nonempty == 1)
+    return multi_single(c, algo, input(first) == rbufs[first] ? BINE_IN_PLACE : input(first), rbufs[first], total,
+                        dtype, op, scale, wide, segsize, stream);
+  hipStream_t K = (hipStream_t)stream;
+  const size_t phase = ((uintptr_t)input(first) & 15) & ~(esz - 1);  // esz: 1, 2, 4, 8 or 16
+  const size_t need = (total * esz + 16 + 255) & ~(size_t)255;
+  char *ws;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (need > c->multi_ws_bytes) {
+      // the old workspace may still be read by enqueued work, and cached
+      // graphs of the inner call hold its address
+      HIP_TRY(hipStreamSynchronize(K));
+      HIP_TRY(hipStreamSynchronize(c->cstream));
+      c->drop_graphs();
+      if (c->multi_ws) HIP_TRY(hipFree(c->multi_ws));
+      c->multi_ws = nullptr;
+      c->multi_ws_bytes = 0;
+      HIP_TRY(hipMalloc(&c->multi_ws, need));
+      c->multi_ws_bytes = need;
+    }
+    ws = (char *)c->multi_ws + phase;
+  }
+  std::vector<void *> packed(n);
+  std::vector<const void *> in(n);
+  std::vector<size_t> bytes(n);
+  size_t off = 0;
+  for (int k = 0; k < n; k++) {
+    packed[k] = ws + off;
+    in[k] = input(k);
+    bytes[k] = counts[k] * esz;
+    off += bytes[k];
+  }
+  int rc = launch_copy_segments(n, packed.data(), in.data(), bytes.data(), K);
+  if (rc) return rc;
+  rc = multi_single(c, algo, BINE_IN_PLACE, ws, total, dtype, op, scale, wide, segsize, K);
+  if (rc) return rc;
+  return launch_copy_segments(n, rbufs, packed.data(), bytes.data(), K);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -2595,6 +2692,25 @@ int bine_loopback_run_allreduce_wide(bine_comm_t *comms, int n, int algo, const 
     (void)hipSetDevice(comms[r]->device);
     return bine_allreduce_wide(comms[r], algo, sbufs[r], rbufs[r], count, dtype, op, scale, segsize,
                                comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_allreduce_multi(bine_comm_t *comms, int nranks, int algo, int n, const void *const *sbufs,
+                                      void *const *rbufs, const size_t *counts, int dtype, int op, double scale,
+                                      int wide, size_t segsize, int *statuses) {
+  // before any thread, stream or HIP call: what every rank would refuse alike
+  auto sb = [&](int r) { return sbufs && n > 0 ? sbufs + (size_t)r * n : sbufs; };
+  auto rb = [&](int r) { return rbufs && n > 0 ? rbufs + (size_t)r * n : rbufs; };
+  int bad = BINE_SUCCESS;
+  for (int r = 0; !bad && r < nranks; r++) bad = multi_args(algo, n, sb(r), rb(r), counts, dtype, op, scale, wide);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return bad;
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_allreduce_multi(comms[r], algo, n, sb(r), rb(r), counts, dtype, op, scale, wide, segsize,
+                                comms[r]->stream);
   });
 }
 

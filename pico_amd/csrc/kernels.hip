@@ -581,6 +581,139 @@ int launch_copy(void *dst, const void *src, size_t bytes, void *stream) {
   return hipGetLastError() == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
 }
 
+// ----------------------------------------------------------------------------
+// segmented copy (bine_copy_segments): up to kSegsPerLaunch independent copies
+// in one launch, the descriptors by value in the kernel arguments (no device
+// table to upload, nothing a later call could overwrite while this launch
+// still reads it).  The grid is the concatenation of every segment's tiles, a
+// tile being k_copy's; a workgroup finds its segment by a binary search over
+// the prefix of tile counts (7 steps of scalar loads: every value is
+// workgroup-uniform) and then is k_copy on that segment, its first workgroup
+// copying the head / tail bytes.  Where the source is not co-aligned with the
+// destination mod 16 B the workgroup loads the two 16-B ALIGNED source
+// vectors that hold a destination vector's bytes and shifts them together in
+// registers: no unaligned vector access is issued, the stores stay 16-B
+// aligned, and the extra bytes read lie in 16-B lines that also hold bytes of
+// the segment, so never in another page.
+static_assert(kCopyTileVecs == (uint64_t)kBlock * kCopyU, "the planner's tile is k_copy's");
+
+struct CopySeg {
+  const uint8_t *src;
+  uint8_t *dst;
+  uint64_t bytes;
+};
+struct CopySegs {
+  uint32_t nseg;
+  uint32_t tile0[kSegsPerLaunch + 1];
+  CopySeg s[kSegsPerLaunch];
+};
+static_assert(sizeof(CopySegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+
+// bytes [sh, sh + 16) of the 32 bytes lo : hi, 0 < sh < 16; W = sh / 4
+template <int W>
+__device__ __forceinline__ u32x4 shift_join(u32x4 lo, u32x4 hi, unsigned bits) {
+  const uint32_t c[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  u32x4 r;
+  r.x = (uint32_t)((((uint64_t)c[W + 1] << 32) | c[W]) >> bits);
+  r.y = (uint32_t)((((uint64_t)c[W + 2] << 32) | c[W + 1]) >> bits);
+  r.z = (uint32_t)((((uint64_t)c[W + 3] << 32) | c[W + 2]) >> bits);
+  r.w = (uint32_t)((((uint64_t)c[W + 4] << 32) | c[W + 3]) >> bits);
+  return r;
+}
+
+constexpr int kCopyShiftU = 4;  // destination vectors per lane in flight on the shifted path
+
+template <int W>
+__device__ __forceinline__ void copy_shifted(const u32x4 *va, u32x4 *vd, size_t base, size_t nvec, unsigned bits) {
+#pragma unroll 1  // keeps the kernel at k_copy's occupancy: the co-aligned path is the fast one
+  for (int u0 = 0; u0 < kCopyU; u0 += kCopyShiftU) {
+    u32x4 lo[kCopyShiftU], hi[kCopyShiftU];
+#pragma unroll
+    for (int u = 0; u < kCopyShiftU; u++) {
+      const size_t i = base + (size_t)(u0 + u) * kBlock;
+      if (i < nvec) {
+        lo[u] = __builtin_nontemporal_load(va + i);
+        hi[u] = __builtin_nontemporal_load(va + i + 1);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kCopyShiftU; u++) {
+      const size_t i = base + (size_t)(u0 + u) * kBlock;
+      if (i < nvec) __builtin_nontemporal_store(shift_join<W>(lo[u], hi[u], bits), vd + i);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_copy_segs(CopySegs a) {
+  const uint32_t t = blockIdx.x;
+  uint32_t k = 0, hi = a.nseg;  // tile0[k] <= t < tile0[hi]
+  while (hi - k > 1) {
+    const uint32_t mid = (k + hi) >> 1;
+    if (t >= a.tile0[mid]) k = mid;
+    else hi = mid;
+  }
+  const uint8_t *__restrict__ src = a.s[k].src;
+  uint8_t *__restrict__ dst = a.s[k].dst;
+  const size_t n = a.s[k].bytes;
+  const uint32_t wt = t - a.tile0[k];
+  const size_t h = (16 - ((uintptr_t)dst & 15)) & 15, head = h < n ? h : n, nvec = (n - head) / 16;
+  if (wt == 0) {  // head and tail of this segment
+    for (size_t i = threadIdx.x; i < head; i += kBlock) dst[i] = src[i];
+    for (size_t i = head + nvec * 16 + threadIdx.x; i < n; i += kBlock) dst[i] = src[i];
+  }
+  u32x4 *vd = reinterpret_cast<u32x4 *>(dst + head);
+  const size_t base = (size_t)wt * kBlock * kCopyU + threadIdx.x;
+  const unsigned sh = (unsigned)((uintptr_t)(src + head) & 15);
+  if (sh == 0) {  // co-aligned: k_copy
+    const u32x4 *vs = reinterpret_cast<const u32x4 *>(src + head);
+    if (base + (kCopyU - 1) * (size_t)kBlock < nvec) {
+      u32x4 x[kCopyU];
+#pragma unroll
+      for (int u = 0; u < kCopyU; u++) x[u] = __builtin_nontemporal_load(vs + base + (size_t)u * kBlock);
+#pragma unroll
+      for (int u = 0; u < kCopyU; u++) __builtin_nontemporal_store(x[u], vd + base + (size_t)u * kBlock);
+    } else {
+#pragma unroll
+      for (int u = 0; u < kCopyU; u++) {
+        const size_t i = base + (size_t)u * kBlock;
+        if (i < nvec) vd[i] = vs[i];
+      }
+    }
+    return;
+  }
+  if (nvec == 0) return;  // nothing but head / tail bytes: no vector of the source is touched
+  // destination vector i = bytes [sh, sh + 16) of the aligned source vectors i, i + 1
+  const u32x4 *va = reinterpret_cast<const u32x4 *>(src + head - sh);
+  const unsigned bits = 8 * (sh & 3);
+  switch (sh >> 2) {
+    case 0: copy_shifted<0>(va, vd, base, nvec, bits); break;
+    case 1: copy_shifted<1>(va, vd, base, nvec, bits); break;
+    case 2: copy_shifted<2>(va, vd, base, nvec, bits); break;
+    default: copy_shifted<3>(va, vd, base, nvec, bits); break;
+  }
+}
+
+int launch_copy_segments(int n, void *const *dsts, const void *const *srcs, const size_t *bytes, void *stream) {
+  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!dsts || !srcs || !bytes))) return BINE_ERR_ARG;
+  uint64_t da[BINE_MULTI_MAX], sa[BINE_MULTI_MAX];
+  for (int k = 0; k < n; k++) da[k] = (uint64_t)(uintptr_t)dsts[k], sa[k] = (uint64_t)(uintptr_t)srcs[k];
+  std::vector<SegLaunch> ls;
+  if (const int rc = plan_seg_launches(n, da, sa, bytes, ls)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  for (const SegLaunch &L : ls) {
+    CopySegs a;
+    a.nseg = (uint32_t)L.nseg;
+    for (int s = 0; s < L.nseg; s++) {
+      a.tile0[s] = L.tile0[s];
+      a.s[s] = {(const uint8_t *)srcs[L.seg[s]], (uint8_t *)dsts[L.seg[s]], (uint64_t)bytes[L.seg[s]]};
+    }
+    for (int s = L.nseg; s <= kSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nseg];
+    for (int s = L.nseg; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, nullptr, 0};
+    hipLaunchKernelGGL(k_copy_segs, dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
+    if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+  }
+  return BINE_SUCCESS;
+}
 
 #endif  // BINE_OPSET == 0
 
