@@ -332,6 +332,36 @@ int bine_copy_segments(int n, void *const *dsts, const void *const *srcs, const 
  * number of tiles (may exceed cap) or -status. */
 int64_t bine_plan_segments(int n, const uint64_t *dst_addr, const uint64_t *src_addr, const size_t *bytes,
                            uint64_t *out, int64_t cap);
+/* The layout change of a sharded bucket: all `nranks` shards of n tensors
+ * copied between two layouts, stream-ordered, one descriptor per TENSOR.
+ *   flat side    tensor k at flat[k], nranks * shard_bytes[k] bytes; shard j
+ *                is [j * shard_bytes[k], (j + 1) * shard_bytes[k])
+ *   packed side  one base pointer; block_bytes = the sum of shard_bytes[k];
+ *                shard j of tensor k is at packed + j * block_bytes + off[k],
+ *                off[k] = the prefix sum of shard_bytes over the tensors
+ *                before k
+ * dir == 0 copies flat -> packed (the reduce-scatter's pack), dir == 1 packed
+ * -> flat (the allgather's unpack).  ceil(nonempty / BINE_COPY_SEGS_PER_LAUNCH)
+ * launches of k_copy_shards, the descriptors by value as k_copy_segs' are; a
+ * launch ends earlier where the next tensor would take it past the grid limit
+ * of one launch (2^24 - 1 workgroups, one per 32 KiB tile of one shard).  A
+ * tensor with shard_bytes[k] == 0 is skipped and its pointer may be NULL;
+ * n == 0 or every tensor empty is success without a launch.  Any alignment,
+ * as bine_copy_segments; the destination ranges must not overlap each other
+ * or any source range.  BINE_ERR_ARG: n < 0, n > BINE_MULTI_MAX, nranks < 1 or
+ * nranks > 64 (the library's peer limit), dir not 0 or 1, a NULL array with
+ * n > 0, a NULL pointer (flat[k], or packed) with a non-zero size, a tensor
+ * that alone exceeds one launch's grid. */
+int bine_copy_shards(int n, int nranks, int dir, void *packed, void *const *flat, const size_t *shard_bytes,
+                     void *stream);
+/* The tile table of that call (host only; the launcher walks the same table):
+ * 6 words per tile -- (launch, tensor, shard, byte offset in the shard, bytes,
+ * kind), kind as in bine_plan_segments, relative to the shard's destination.
+ * Only tiles that copy bytes are listed (a tensor's shards share one tile
+ * count, the largest any of them needs; the surplus workgroups copy nothing).
+ * Returns the number of tiles (may exceed cap) or -status. */
+int64_t bine_plan_shards(int n, int nranks, int dir, uint64_t packed_addr, const uint64_t *flat_addr,
+                         const size_t *shard_bytes, uint64_t *out, int64_t cap);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -689,11 +719,61 @@ int bine_reduce_scatter_wide(bine_comm_t comm, int algo, const void *sbuf, void 
  * `comm` is looked at); n < 0 or n > BINE_MULTI_MAX; counts == NULL or
  * rbufs == NULL with n > 0; a NULL buffer with a non-zero count.  Then an
  * algorithm id outside the allreduce range is BINE_ERR_UNSUPPORTED as in
- * bine_allreduce, and comm == NULL is BINE_ERR_ARG.  Not provided: a
- * reduce-scatter / allgather / rooted form, mixed element types. */
+ * bine_allreduce, and comm == NULL is BINE_ERR_ARG.  Not provided: a rooted
+ * form, mixed element types (the sharded reduce-scatter / allgather forms
+ * follow). */
 int bine_allreduce_multi(bine_comm_t comm, int algo, int n, const void *const *sbufs, void *const *rbufs,
                          const size_t *counts, int dtype, int op, double scale, int wide, size_t segsize,
                          void *stream);
+/* ---- sharded multi-buffer reduce-scatter and allgather ------------------------
+ * What sharded training does with a bucket of n tensors on every step.  Let
+ * c_k = shard_counts[k] elements, B = the sum of the c_k, P = the number of
+ * ranks; every rank passes the same n and shard_counts.
+ * bine_reduce_scatter_multi: sbufs[k] holds P * c_k elements, rbufs[k]
+ * receives c_k.  Let M be the packed buffer whose block j is the
+ * concatenation over k of sbufs[k][j * c_k : (j + 1) * c_k].  The call leaves
+ * in rbufs[k] the k-th slice of what ONE single-buffer call writes to its
+ * rbuf, bit for bit: out of place, on M, rcounts[j] = B for every j, the same
+ * algorithm and communicator settings --
+ *   wide == 0, scale == 1.0   bine_reduce_scatter
+ *   wide == 0, scale != 1.0   bine_reduce_scatter_scaled
+ *   wide != 0, any scale      bine_reduce_scatter_wide
+ * Mechanism: bine_copy_shards (dir 0) packs M into the communicator's multi
+ * workspace, the single call runs there, bine_copy_segments unpacks the
+ * received block into rbufs.
+ * bine_allgather_multi: sbufs[k] holds c_k elements, rbufs[k] receives
+ * P * c_k; rbufs[k][j * c_k : (j + 1) * c_k] is rank j's sbufs[k].  sbufs ==
+ * NULL, or sbufs[k] == BINE_IN_PLACE: tensor k's input is rbufs[k] + rank *
+ * c_k elements (MPI's in-place convention, for every algorithm).  Mechanism:
+ * bine_copy_segments packs the n shards into one block of the workspace, the
+ * single bine_allgather runs there OUT OF PLACE with count = B (so the
+ * per-algorithm in-place placements never come into play), bine_copy_shards
+ * (dir 1) unpacks.
+ * Both: every input is packed before any output is written, so an output
+ * range may overlap any input range of the same call (gathering into the
+ * tensor that holds one's own shard is legal); output ranges must not overlap
+ * each other.  All on the caller's stream, no host synchronization in steady
+ * state; the workspace is bine_allreduce_multi's, grown by its rule; pack and
+ * unpack are ordinary launches, never captured; with graph mode on the inner
+ * call is captured and replayed as any call on that address.  A tensor with
+ * c_k == 0 is skipped and its pointers may be NULL.  A call with exactly one
+ * non-empty tensor whose input and output do not overlap is the single call
+ * on the caller's own buffers.  B == 0: success, nothing is written.
+ * BINE_ERR_ARG, on every rank alike, before any exchange and any HIP call, in
+ * this order: a (dtype, op) pair the selected family refuses (reduce-scatter
+ * only; checked before `comm` is looked at); n < 0 or n > BINE_MULTI_MAX;
+ * shard_counts == NULL or rbufs == NULL with n > 0; sbufs == NULL with n > 0
+ * (reduce-scatter); a NULL buffer with a non-zero count; B > INT_MAX
+ * (reduce-scatter: rcounts is int).  Then an algorithm id outside the
+ * collective's range is BINE_ERR_UNSUPPORTED as in the single call, and comm
+ * == NULL is BINE_ERR_ARG.  Whatever the single call refuses (a P the
+ * algorithm does not support, a wide or scaled form it does not have) is
+ * returned as it returns it; P above bine_copy_shards' 64 is BINE_ERR_ARG.
+ * Not provided: rooted forms, unequal shards, mixed element types. */
+int bine_reduce_scatter_multi(bine_comm_t comm, int algo, int n, const void *const *sbufs, void *const *rbufs,
+                              const size_t *shard_counts, int dtype, int op, double scale, int wide, void *stream);
+int bine_allgather_multi(bine_comm_t comm, int algo, int n, const void *const *sbufs, void *const *rbufs,
+                         const size_t *shard_counts, int dtype, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -773,6 +853,15 @@ int bine_loopback_run_allreduce_multi(bine_comm_t *comms, int nranks, int algo, 
                                       const void *const *sbufs, void *const *rbufs, const size_t *counts,
                                       int dtype, int op, double scale, int wide, size_t segsize,
                                       int *statuses);
+/* the sharded forms: nranks * n pointers, rank r's tensor k at [r * n + k]
+ * (allgather: sbufs NULL = every tensor in place) */
+int bine_loopback_run_reduce_scatter_multi(bine_comm_t *comms, int nranks, int algo, int n,
+                                           const void *const *sbufs, void *const *rbufs,
+                                           const size_t *shard_counts, int dtype, int op, double scale, int wide,
+                                           int *statuses);
+int bine_loopback_run_allgather_multi(bine_comm_t *comms, int nranks, int algo, int n,
+                                      const void *const *sbufs, void *const *rbufs, const size_t *shard_counts,
+                                      int dtype, int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

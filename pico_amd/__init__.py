@@ -29,6 +29,12 @@ list of tensors as ONE collective -- the slices of the single call on their
 concatenation, bit for bit (plain, ``scale=`` / ``op="avg"``, ``wide=True``).
 ``copy_segments`` is the many-ranges-one-launch device copy that packs and
 unpacks them.
+
+Sharded multi-buffer forms: ``reduce_scatter_multi`` leaves every rank its 1/P
+shard of EACH tensor of a bucket, ``allgather_multi`` gathers a bucket of shards
+back into the full tensors, each as ONE collective on the rank-major packing.
+``copy_shards`` is the strided device copy (one descriptor per tensor) between
+the two layouts.
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

@@ -175,6 +175,12 @@ def lib():
         "bine_plan_segments": ([i, vp, vp, vp, vp, ctypes.c_int64], ctypes.c_int64),
         "bine_allreduce_multi": ([vp, i, i, vp, vp, vp, i, i, ctypes.c_double, i, sz, vp], i),
         "bine_loopback_run_allreduce_multi": ([vp, i, i, i, vp, vp, vp, i, i, ctypes.c_double, i, sz, vp], i),
+        "bine_copy_shards": ([i, i, i, vp, vp, vp, vp], i),
+        "bine_plan_shards": ([i, i, i, u64, vp, vp, vp, ctypes.c_int64], ctypes.c_int64),
+        "bine_reduce_scatter_multi": ([vp, i, i, vp, vp, vp, i, i, ctypes.c_double, i, vp], i),
+        "bine_allgather_multi": ([vp, i, i, vp, vp, vp, i, vp], i),
+        "bine_loopback_run_reduce_scatter_multi": ([vp, i, i, i, vp, vp, vp, i, i, ctypes.c_double, i, vp], i),
+        "bine_loopback_run_allgather_multi": ([vp, i, i, i, vp, vp, vp, i, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

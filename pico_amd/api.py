@@ -536,6 +536,121 @@ def loopback_allreduce_multi(comms, algo, sbufs, rbufs, dtype, op="sum", counts=
     return rc, list(st)
 
 
+# ---- sharded multi-buffer forms: reduce-scatter / allgather of a bucket ----------------
+
+def copy_shards(packed, flat, shard_bytes: Sequence[int], nranks: int, dir: int, stream=None) -> None:
+    """All `nranks` shards of every tensor copied between the flat layout (shard
+    j of tensor k at flat[k] + j * shard_bytes[k]) and the packed one (at packed
+    + j * sum(shard_bytes) + the prefix sum of shard_bytes before k), in
+    ceil(non-empty / COPY_SEGS_PER_LAUNCH) launches of k_copy_shards
+    (bine_copy_shards).  dir 0: flat -> packed, dir 1: packed -> flat.  Any
+    alignment; empty tensors may be None."""
+    n = len(shard_bytes)
+    if len(flat) != n:
+        raise ValueError("copy_shards: flat and shard_bytes differ in length")
+    check(lib().bine_copy_shards(n, nranks, dir, _ptr(packed), _ptrs(flat),
+                                 (ctypes.c_size_t * max(n, 1))(*shard_bytes), _stream(stream, None)),
+          "bine_copy_shards")
+
+
+def plan_shards(packed_addr: int, flat_addrs: Sequence[int], shard_bytes: Sequence[int], nranks: int, dir: int):
+    """The tile table of that call (bine_plan_shards, host only): a list of
+    (launch, tensor, shard, byte offset in the shard, bytes, kind), kind 0 = a
+    vector tile, 1 = head / tail bytes; only tiles that copy bytes."""
+    n = len(shard_bytes)
+    if len(flat_addrs) != n:
+        raise ValueError("plan_shards: flat_addrs and shard_bytes differ in length")
+    f = (ctypes.c_uint64 * max(n, 1))(*flat_addrs)
+    b = (ctypes.c_size_t * max(n, 1))(*shard_bytes)
+    nt = lib().bine_plan_shards(n, nranks, dir, packed_addr, f, b, None, 0)
+    if nt < 0:
+        raise BineError(int(-nt), "bine_plan_shards")
+    out = (ctypes.c_uint64 * max(6 * int(nt), 1))()
+    lib().bine_plan_shards(n, nranks, dir, packed_addr, f, b, out, nt)
+    return [tuple(int(x) for x in out[6 * k:6 * k + 6]) for k in range(int(nt))]
+
+
+def _shard_counts(name: str, rbufs, shard_counts, per: int):
+    """shard_counts=None: each rbuf's numel() // per (reduce-scatter: per = 1,
+    rbufs[k] IS a shard; allgather: per = comm.size, rbufs[k] holds them all)"""
+    if shard_counts is None:
+        shard_counts = []
+        for b in rbufs:
+            if b.numel() % per:
+                raise ValueError(f"{name}: a tensor of {b.numel()} elements does not split into {per} equal shards")
+            shard_counts.append(b.numel() // per)
+    if len(shard_counts) != len(rbufs):
+        raise ValueError(f"{name}: shard_counts and rbufs differ in length")
+    return (ctypes.c_size_t * max(len(shard_counts), 1))(*shard_counts)
+
+
+def reduce_scatter_multi(algo, sbufs, rbufs, dtype, op: str, comm: Comm, shard_counts=None, stream=None,
+                         scale=None, wide: bool = False) -> None:
+    """bine_reduce_scatter_multi: sbufs[k] holds comm.size shards of
+    shard_counts[k] elements, rbufs[k] receives this rank's reduced shard --
+    the slices of ONE reduce_scatter (scale= / op="avg": the scaled call,
+    wide=True: reduce_scatter_wide) on the rank-major packing of the shards,
+    bit for bit.  rbufs[k] may overlap sbufs[k].  shard_counts (the same on
+    every rank) defaults to each rbuf's numel()."""
+    if sbufs is None or len(sbufs) != len(rbufs):
+        raise ValueError("reduce_scatter_multi: sbufs and rbufs differ in length")
+    op, scale = _multi_family(op, scale, wide, comm)
+    c = _shard_counts("reduce_scatter_multi", rbufs, shard_counts, 1)
+    check(lib().bine_reduce_scatter_multi(comm.handle, _algo("reduce_scatter", algo), len(rbufs), _ptrs(sbufs),
+                                          _ptrs(rbufs), c, _dtype(dtype, *rbufs), OPS[op], scale, int(bool(wide)),
+                                          _stream(stream, comm)), f"reduce_scatter_{algo} (multi)")
+
+
+def allgather_multi(algo, sbufs, rbufs, dtype, comm: Comm, shard_counts=None, stream=None) -> None:
+    """bine_allgather_multi: rbufs[k][j * c : (j + 1) * c] = rank j's sbufs[k]
+    (c = shard_counts[k] elements) for every tensor, as ONE allgather.
+    sbufs=None, or sbufs[k] IN_PLACE: tensor k's input is its own shard's place
+    in rbufs[k]; sbufs[k] may be any view into rbufs[k].  shard_counts (the
+    same on every rank) defaults to each rbuf's numel() // comm.size."""
+    if sbufs is not None and len(sbufs) != len(rbufs):
+        raise ValueError("allgather_multi: sbufs and rbufs differ in length")
+    c = _shard_counts("allgather_multi", rbufs, shard_counts, 1 if shard_counts is not None else comm.size)
+    check(lib().bine_allgather_multi(comm.handle, _algo("allgather", algo), len(rbufs),
+                                     None if sbufs is None else _ptrs(sbufs), _ptrs(rbufs), c,
+                                     _dtype(dtype, *rbufs), _stream(stream, comm)), f"allgather_{algo} (multi)")
+
+
+def _rank_lists(name: str, sbufs, rbufs):
+    n = len(rbufs[0])
+    if any(len(r) != n for r in rbufs) or (sbufs is not None and any(len(s) != n for s in sbufs)):
+        raise ValueError(f"{name}: the ranks' lists differ in length")
+    flat_r = [b for r in rbufs for b in r]
+    return n, flat_r, None if sbufs is None else _ptrs([b for s in sbufs for b in s])
+
+
+def loopback_reduce_scatter_multi(comms, algo, sbufs, rbufs, dtype, op="sum", shard_counts=None, scale=None,
+                                  wide=False):
+    """sbufs / rbufs: one list of tensors per virtual rank.  Returns (status,
+    per-rank statuses)."""
+    st = (ctypes.c_int * len(comms))()
+    hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
+    op, scale = _multi_family(op, scale, wide, comms[0])
+    n, flat_r, flat_s = _rank_lists("loopback_reduce_scatter_multi", sbufs, rbufs)
+    c = _shard_counts("loopback_reduce_scatter_multi", rbufs[0], shard_counts, 1)
+    rc = lib().bine_loopback_run_reduce_scatter_multi(hs, len(comms), _algo("reduce_scatter", algo), n, flat_s,
+                                                      _ptrs(flat_r), c, _dtype(dtype, *flat_r), OPS[op], scale,
+                                                      int(bool(wide)), st)
+    return rc, list(st)
+
+
+def loopback_allgather_multi(comms, algo, sbufs, rbufs, dtype, shard_counts=None):
+    """sbufs (None: in place) / rbufs: one list of tensors per virtual rank.
+    Returns (status, per-rank statuses)."""
+    st = (ctypes.c_int * len(comms))()
+    hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
+    n, flat_r, flat_s = _rank_lists("loopback_allgather_multi", sbufs, rbufs)
+    c = _shard_counts("loopback_allgather_multi", rbufs[0], shard_counts,
+                      1 if shard_counts is not None else len(comms))
+    rc = lib().bine_loopback_run_allgather_multi(hs, len(comms), _algo("allgather", algo), n, flat_s, _ptrs(flat_r),
+                                                 c, _dtype(dtype, *flat_r), st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -924,6 +1039,8 @@ __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fus
            "rccl_version", "scale", "scale_valid", "wide_valid", "widen", "narrow", "reduce_tree_wide",
            "allreduce_wide", "reduce_scatter_wide", "loopback_allreduce_wide", "loopback_reduce_scatter_wide",
            "wide_plan", "copy_segments", "plan_segments", "allreduce_multi", "loopback_allreduce_multi",
+           "copy_shards", "plan_shards", "reduce_scatter_multi", "allgather_multi",
+           "loopback_reduce_scatter_multi", "loopback_allgather_multi",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

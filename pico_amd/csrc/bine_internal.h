@@ -220,6 +220,39 @@ struct SegLaunch {
 int plan_seg_launches(int n, const uint64_t *dst_addr, const uint64_t *src_addr, const size_t *bytes,
                       std::vector<SegLaunch> &out);
 int launch_copy_segments(int n, void *const *dsts, const void *const *srcs, const size_t *bytes, void *stream);
+// sharded copy (bine_copy_shards): all P shards of up to kSegsPerLaunch
+// non-empty tensors per launch of k_copy_shards, between the flat layout
+// (shard j of tensor k at flat[k] + j * bytes[k]) and the packed one (at
+// packed + j * block_bytes + poff[k], poff = the prefix sum of bytes over the
+// non-empty tensors).  Every shard of a tensor gets tps tiles, tps = what the
+// shard with the most destination vectors needs (at least one); with T = the
+// sum of tps over the launch's tensors the grid is P * T workgroups, shard
+// major: workgroup t is tile t % T (of the tensors' concatenated tiles) of
+// shard t / T, and copies nothing where that shard has fewer tiles.
+constexpr int kShardMaxRanks = 64;  // the library's peer limit (dm::kMaxPeers)
+struct ShardLaunch {
+  int nten = 0;
+  int ten[kSegsPerLaunch];             // the caller's tensor index per slot
+  uint64_t poff[kSegsPerLaunch];       // its shards' offset in a packed block
+  uint32_t tile0[kSegsPerLaunch + 1];  // first tile per slot within one shard's T; [nten] = T
+};
+// the destination of shard j of a tensor (dir 0: packed, dir 1: flat) and the
+// split of its bytes, the expressions k_copy_shards evaluates too
+inline uint64_t shard_dst(int dir, uint64_t packed, uint64_t block_bytes, uint64_t poff, uint64_t flat,
+                          uint64_t bytes, uint64_t j) {
+  return dir ? flat + j * bytes : packed + j * block_bytes + poff;
+}
+inline uint64_t shard_head(uint64_t dst, uint64_t bytes) {
+  const uint64_t h = (16 - (dst & 15)) & 15;
+  return h < bytes ? h : bytes;
+}
+// BINE_SUCCESS, or BINE_ERR_ARG (n, nranks or dir out of range, a NULL array, a
+// zero address with a non-zero size, a tensor that alone exceeds kSegMaxWgs
+// workgroups); a launch ends early where the next tensor would pass kSegMaxWgs
+int plan_shard_launches(int n, int nranks, int dir, uint64_t packed_addr, const uint64_t *flat_addr,
+                        const size_t *bytes, std::vector<ShardLaunch> &out, uint64_t *block_bytes);
+int launch_copy_shards(int n, int nranks, int dir, void *packed, void *const *flat, const size_t *bytes,
+                       void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -2044,6 +2044,11 @@ int bine_copy_segments(int n, void *const *dsts, const void *const *srcs, const 
   return launch_copy_segments(n, dsts, srcs, bytes, stream);  // its planner checks the arguments
 }
 
+int bine_copy_shards(int n, int nranks, int dir, void *packed, void *const *flat, const size_t *shard_bytes,
+                     void *stream) {
+  return launch_copy_shards(n, nranks, dir, packed, flat, shard_bytes, stream);  // likewise
+}
+
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream) {
   return launch_fill_pico(buf, count, dtype, seed, stream);
 }
@@ -2416,6 +2421,26 @@ static int multi_args(int algo, int n, const void *const *sbufs, void *const *rb
   return BINE_SUCCESS;
 }
 
+// the communicator's multi workspace, at least `need` bytes (a multiple of 256)
+static int multi_workspace(bine_comm_t c, size_t need, hipStream_t K, char **ws) {
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  if (need > c->multi_ws_bytes) {
+    // the old workspace may still be read by enqueued work, and cached
+    // graphs of the inner call hold its address
+    HIP_TRY(hipStreamSynchronize(K));
+    HIP_TRY(hipStreamSynchronize(c->cstream));
+    c->drop_graphs();
+    if (c->multi_ws) HIP_TRY(hipFree(c->multi_ws));
+    c->multi_ws = nullptr;
+    c->multi_ws_bytes = 0;
+    HIP_TRY(hipMalloc(&c->multi_ws, need));
+    c->multi_ws_bytes = need;
+  }
+  *ws = (char *)c->multi_ws;
+  return BINE_SUCCESS;
+}
+
 // Pack (bine_copy_segments) into the communicator's workspace, the single
 // call there in place, unpack into rbufs: wide_path_a's pattern, all on the
 // caller's stream.  The packed region starts at the first non-empty input's
@@ -2443,25 +2468,9 @@ int bine_allreduce_multi(bine_comm_t c, int algo, int n, const void *const *sbuf
                         dtype, op, scale, wide, segsize, stream);
   hipStream_t K = (hipStream_t)stream;
   const size_t phase = ((uintptr_t)input(first) & 15) & ~(esz - 1);  // esz: 1, 2, 4, 8 or 16
-  const size_t need = (total * esz + 16 + 255) & ~(size_t)255;
   char *ws;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    if (need > c->multi_ws_bytes) {
-      // the old workspace may still be read by enqueued work, and cached
-      // graphs of the inner call hold its address
-      HIP_TRY(hipStreamSynchronize(K));
-      HIP_TRY(hipStreamSynchronize(c->cstream));
-      c->drop_graphs();
-      if (c->multi_ws) HIP_TRY(hipFree(c->multi_ws));
-      c->multi_ws = nullptr;
-      c->multi_ws_bytes = 0;
-      HIP_TRY(hipMalloc(&c->multi_ws, need));
-      c->multi_ws_bytes = need;
-    }
-    ws = (char *)c->multi_ws + phase;
-  }
+  if (const int rc = multi_workspace(c, (total * esz + 16 + 255) & ~(size_t)255, K, &ws)) return rc;
+  ws += phase;
   std::vector<void *> packed(n);
   std::vector<const void *> in(n);
   std::vector<size_t> bytes(n);
@@ -2477,6 +2486,148 @@ int bine_allreduce_multi(bine_comm_t c, int algo, int n, const void *const *sbuf
   rc = multi_single(c, algo, BINE_IN_PLACE, ws, total, dtype, op, scale, wide, segsize, K);
   if (rc) return rc;
   return launch_copy_segments(n, rbufs, packed.data(), bytes.data(), K);
+}
+
+// ---- sharded multi-buffer reduce-scatter / allgather (bine_amd.h) ---------------------
+
+// the checks that need no communicator, in the header's order; `rs`: the
+// reduce-scatter (a (dtype, op) pair, sbufs required, B within int)
+static int shard_args(bool rs, int algo, int n, const void *const *sbufs, void *const *rbufs,
+                      const size_t *shard_counts, int dtype, int op, double scale, int wide) {
+  if (rs) {
+    const int ok = wide ? bine_wide_valid(dtype, op) : scale != 1.0 ? bine_scale_valid(dtype, op)
+                                                                    : bine_op_valid(dtype, op);
+    if (!ok) return BINE_ERR_ARG;
+  }
+  if (n < 0 || n > BINE_MULTI_MAX) return BINE_ERR_ARG;
+  if (n > 0 && (!shard_counts || !rbufs)) return BINE_ERR_ARG;
+  if (rs && n > 0 && !sbufs) return BINE_ERR_ARG;
+  size_t total = 0;
+  for (int k = 0; k < n; k++) {
+    if (!shard_counts[k]) continue;
+    if (!rbufs[k] || (sbufs && !sbufs[k])) return BINE_ERR_ARG;
+    if (shard_counts[k] > (size_t)INT_MAX) return BINE_ERR_ARG;  // keeps the sum below 2^64 too
+    total += shard_counts[k];
+  }
+  if (rs && total > (size_t)INT_MAX) return BINE_ERR_ARG;  // rcounts is int
+  if (rs ? algo < BINE_RS_RECURSIVEHALVING || algo > BINE_RS_BINE_BLOCK_BY_BLOCK_ANY_EVEN
+         : algo < BINE_AG_RECURSIVEDOUBLING || algo > BINE_AG_BINE_2_BLOCKS_DTYPE)
+    return BINE_ERR_UNSUPPORTED;
+  return BINE_SUCCESS;
+}
+
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+// the workspace of a sharded call: one block of `block` bytes at `one` and P
+// blocks at `all`, each at its own 16-B phase so that equally aligned tensors
+// stay co-aligned with their packed ranges
+static int shard_workspace(bine_comm_t c, size_t block, size_t phase_one, size_t phase_all, hipStream_t K,
+                           char **one, char **all) {
+  const size_t one_bytes = (block + 16 + 255) & ~(size_t)255;
+  const size_t need = one_bytes + (((size_t)c->size * block + 16 + 255) & ~(size_t)255);
+  char *ws;
+  if (const int rc = multi_workspace(c, need, K, &ws)) return rc;
+  *one = ws + phase_one;
+  *all = ws + one_bytes + phase_all;
+  return BINE_SUCCESS;
+}
+
+// bine_copy_shards packs the P-shard inputs rank-major into the workspace, the
+// single reduce-scatter runs there out of place with rcounts[j] = B, and
+// bine_copy_segments unpacks the received block into rbufs
+int bine_reduce_scatter_multi(bine_comm_t c, int algo, int n, const void *const *sbufs, void *const *rbufs,
+                              const size_t *shard_counts, int dtype, int op, double scale, int wide,
+                              void *stream) {
+  if (const int rc = shard_args(true, algo, n, sbufs, rbufs, shard_counts, dtype, op, scale, wide)) return rc;
+  if (!c) return BINE_ERR_ARG;
+  const size_t esz = bine_dtype_size(dtype), P = (size_t)c->size;
+  size_t total = 0;
+  int nonempty = 0, first = -1;
+  for (int k = 0; k < n; k++) {
+    if (!shard_counts[k]) continue;
+    if (first < 0) first = k;
+    nonempty++;
+    total += shard_counts[k];
+  }
+  if (nonempty == 0) return BINE_SUCCESS;
+  const std::vector<int> rcounts(P, (int)total);
+  auto single = [&](const void *sbuf, void *rbuf, void *st) {
+    if (wide) return bine_reduce_scatter_wide(c, algo, sbuf, rbuf, rcounts.data(), dtype, op, scale, st);
+    if (scale != 1.0) return bine_reduce_scatter_scaled(c, algo, sbuf, rbuf, rcounts.data(), dtype, op, scale, st);
+    return bine_reduce_scatter(c, algo, sbuf, rbuf, rcounts.data(), dtype, op, st);
+  };
+  if (nonempty == 1 && !ranges_overlap(sbufs[first], P * total * esz, rbufs[first], total * esz))
+    return single(sbufs[first], rbufs[first], stream);
+  hipStream_t K = (hipStream_t)stream;
+  const size_t align = ~(esz - 1);  // esz: 1, 2, 4, 8 or 16
+  char *recv, *send;
+  if (const int rc = shard_workspace(c, total * esz, ((uintptr_t)rbufs[first] & 15) & align,
+                                     ((uintptr_t)sbufs[first] & 15) & align, K, &recv, &send))
+    return rc;
+  std::vector<void *> flat(n), packed(n);
+  std::vector<size_t> bytes(n);
+  size_t off = 0;
+  for (int k = 0; k < n; k++) {
+    flat[k] = const_cast<void *>(sbufs[k]);  // dir 0 only reads the flat side
+    packed[k] = recv + off;
+    bytes[k] = shard_counts[k] * esz;
+    off += bytes[k];
+  }
+  int rc = launch_copy_shards(n, (int)P, 0, send, flat.data(), bytes.data(), K);
+  if (rc) return rc;
+  rc = single(send, recv, K);
+  if (rc) return rc;
+  return launch_copy_segments(n, rbufs, packed.data(), bytes.data(), K);
+}
+
+// bine_copy_segments packs the n shards into one block of the workspace, the
+// single allgather runs there out of place with count = B, and
+// bine_copy_shards unpacks the P gathered blocks into rbufs
+int bine_allgather_multi(bine_comm_t c, int algo, int n, const void *const *sbufs, void *const *rbufs,
+                         const size_t *shard_counts, int dtype, void *stream) {
+  if (const int rc = shard_args(false, algo, n, sbufs, rbufs, shard_counts, dtype, 0, 1.0, 0)) return rc;
+  if (!c) return BINE_ERR_ARG;
+  const size_t esz = bine_dtype_size(dtype), P = (size_t)c->size;
+  if (!esz) return BINE_ERR_ARG;
+  auto input = [&](int k) -> const void * {
+    return !sbufs || sbufs[k] == BINE_IN_PLACE ? (const char *)rbufs[k] + (size_t)c->rank * shard_counts[k] * esz
+                                               : sbufs[k];
+  };
+  size_t total = 0;
+  int nonempty = 0, first = -1;
+  for (int k = 0; k < n; k++) {
+    if (!shard_counts[k]) continue;
+    if (first < 0) first = k;
+    nonempty++;
+    total += shard_counts[k];
+  }
+  if (nonempty == 0) return BINE_SUCCESS;
+  if (nonempty == 1 && !ranges_overlap(input(first), total * esz, rbufs[first], P * total * esz))
+    return bine_allgather(c, algo, input(first), rbufs[first], total, dtype, stream);
+  hipStream_t K = (hipStream_t)stream;
+  const size_t align = ~(esz - 1);
+  char *send, *recv;
+  if (const int rc = shard_workspace(c, total * esz, ((uintptr_t)input(first) & 15) & align,
+                                     ((uintptr_t)rbufs[first] & 15) & align, K, &send, &recv))
+    return rc;
+  std::vector<void *> packed(n);
+  std::vector<const void *> in(n);
+  std::vector<size_t> bytes(n);
+  size_t off = 0;
+  for (int k = 0; k < n; k++) {
+    packed[k] = send + off;
+    in[k] = shard_counts[k] ? input(k) : nullptr;
+    bytes[k] = shard_counts[k] * esz;
+    off += bytes[k];
+  }
+  int rc = launch_copy_segments(n, packed.data(), in.data(), bytes.data(), K);
+  if (rc) return rc;
+  rc = bine_allgather(c, algo, send, recv, total, dtype, K);
+  if (rc) return rc;
+  return launch_copy_shards(n, (int)P, 1, recv, rbufs, bytes.data(), K);
 }
 
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
@@ -2711,6 +2862,43 @@ int bine_loopback_run_allreduce_multi(bine_comm_t *comms, int nranks, int algo, 
     (void)hipSetDevice(comms[r]->device);
     return bine_allreduce_multi(comms[r], algo, n, sb(r), rb(r), counts, dtype, op, scale, wide, segsize,
                                 comms[r]->stream);
+  });
+}
+
+// sbufs / rbufs: nranks * n pointers, rank r's tensor k at [r * n + k]
+int bine_loopback_run_reduce_scatter_multi(bine_comm_t *comms, int nranks, int algo, int n,
+                                           const void *const *sbufs, void *const *rbufs, const size_t *shard_counts,
+                                           int dtype, int op, double scale, int wide, int *statuses) {
+  // before any thread, stream or HIP call: what every rank would refuse alike
+  auto sb = [&](int r) { return sbufs && n > 0 ? sbufs + (size_t)r * n : sbufs; };
+  auto rb = [&](int r) { return rbufs && n > 0 ? rbufs + (size_t)r * n : rbufs; };
+  int bad = BINE_SUCCESS;
+  for (int r = 0; !bad && r < nranks; r++)
+    bad = shard_args(true, algo, n, sb(r), rb(r), shard_counts, dtype, op, scale, wide);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return bad;
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_reduce_scatter_multi(comms[r], algo, n, sb(r), rb(r), shard_counts, dtype, op, scale, wide,
+                                     comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_allgather_multi(bine_comm_t *comms, int nranks, int algo, int n, const void *const *sbufs,
+                                      void *const *rbufs, const size_t *shard_counts, int dtype, int *statuses) {
+  auto sb = [&](int r) { return sbufs && n > 0 ? sbufs + (size_t)r * n : sbufs; };
+  auto rb = [&](int r) { return rbufs && n > 0 ? rbufs + (size_t)r * n : rbufs; };
+  int bad = BINE_SUCCESS;
+  for (int r = 0; !bad && r < nranks; r++) bad = shard_args(false, algo, n, sb(r), rb(r), shard_counts, dtype, 0, 1.0, 0);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return bad;
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_allgather_multi(comms[r], algo, n, sb(r), rb(r), shard_counts, dtype, comms[r]->stream);
   });
 }
 

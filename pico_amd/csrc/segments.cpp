@@ -1,11 +1,14 @@
-// segments.cpp -- the tile table of the segmented copy (bine_copy_segments).
+// segments.cpp -- the tile tables of the segmented copy (bine_copy_segments)
+// and of the sharded copy (bine_copy_shards).
 //
 // Host only, no HIP: plain C++ over addresses and sizes, so the CPU suite can
 // check the cover (bine_plan_segments) and a stand-alone program can run it
 // under the host sanitizers (tools/segments_check.cpp).  launch_copy_segments
 // (kernels.hip) issues exactly the launches plan_seg_launches returns, and
 // k_copy_segs derives a segment's head and vector count from the same two
-// expressions (seg_head / seg_nvec) over the same descriptor.
+// expressions (seg_head / seg_nvec) over the same descriptor.  The sharded
+// copy is built the same way: plan_shard_launches / bine_plan_shards are what
+// launch_copy_shards issues as k_copy_shards (tools/shards_check.cpp).
 #include <algorithm>
 
 #include "bine_internal.h"
@@ -43,7 +46,90 @@ int plan_seg_launches(int n, const uint64_t *dst_addr, const uint64_t *src_addr,
   return BINE_SUCCESS;
 }
 
+// tiles (workgroups) per shard of one tensor: the most any of its shards needs.
+// A shard's tile count depends on its destination's phase mod 16 B, which has a
+// period of at most 16 in j.
+static uint64_t shard_tiles(int nranks, int dir, uint64_t packed, uint64_t block, uint64_t poff, uint64_t flat,
+                            uint64_t bytes) {
+  uint64_t tps = 1;
+  for (int j = 0; j < nranks && j < 16; j++) {
+    const uint64_t nvec = seg_nvec(bytes, shard_head(shard_dst(dir, packed, block, poff, flat, bytes, j), bytes));
+    tps = std::max(tps, (nvec + kCopyTileVecs - 1) / kCopyTileVecs);
+  }
+  return tps;
+}
+
+int plan_shard_launches(int n, int nranks, int dir, uint64_t packed_addr, const uint64_t *flat_addr,
+                        const size_t *bytes, std::vector<ShardLaunch> &out, uint64_t *block_bytes) {
+  out.clear();
+  if (block_bytes) *block_bytes = 0;
+  if (n < 0 || n > BINE_MULTI_MAX) return BINE_ERR_ARG;
+  if (nranks < 1 || nranks > kShardMaxRanks) return BINE_ERR_ARG;
+  if (dir != 0 && dir != 1) return BINE_ERR_ARG;
+  if (n > 0 && (!flat_addr || !bytes)) return BINE_ERR_ARG;
+  uint64_t block = 0;
+  for (int k = 0; k < n; k++) {
+    if (bytes[k] == 0) continue;
+    if (!flat_addr[k] || !packed_addr) return BINE_ERR_ARG;
+    // more than one launch's workgroups for one shard; also keeps every sum below 2^64
+    if (bytes[k] / 16 / kCopyTileVecs > kSegMaxWgs) return BINE_ERR_ARG;
+    block += bytes[k];
+  }
+  if (block_bytes) *block_bytes = block;
+  uint64_t poff = 0;
+  for (int k = 0; k < n; k++) {
+    if (bytes[k] == 0) continue;
+    // tile0 counts tiles per shard; the launch's grid is nranks times its total
+    const uint64_t tps = shard_tiles(nranks, dir, packed_addr, block, poff, flat_addr[k], bytes[k]);
+    if (tps * nranks > kSegMaxWgs) return BINE_ERR_ARG;
+    if (out.empty() || out.back().nten == kSegsPerLaunch ||
+        (out.back().tile0[out.back().nten] + tps) * nranks > kSegMaxWgs) {
+      out.emplace_back();
+      out.back().tile0[0] = 0;
+    }
+    ShardLaunch &L = out.back();
+    const int s = L.nten++;
+    L.ten[s] = k;
+    L.poff[s] = poff;
+    L.tile0[s + 1] = (uint32_t)(L.tile0[s] + tps);
+    poff += bytes[k];
+  }
+  return BINE_SUCCESS;
+}
+
 }  // namespace bine
+
+extern "C" int64_t bine_plan_shards(int n, int nranks, int dir, uint64_t packed_addr, const uint64_t *flat_addr,
+                                    const size_t *shard_bytes, uint64_t *out, int64_t cap) {
+  std::vector<bine::ShardLaunch> ls;
+  uint64_t block = 0;
+  const int rc = bine::plan_shard_launches(n, nranks, dir, packed_addr, flat_addr, shard_bytes, ls, &block);
+  if (rc) return -(int64_t)rc;
+  int64_t nt = 0;
+  auto put = [&](uint64_t launch, uint64_t ten, uint64_t shard, uint64_t off, uint64_t len, uint64_t kind) {
+    if (out && nt < cap) {
+      uint64_t *e = out + 6 * nt;
+      e[0] = launch, e[1] = ten, e[2] = shard, e[3] = off, e[4] = len, e[5] = kind;
+    }
+    nt++;
+  };
+  for (size_t l = 0; l < ls.size(); l++) {
+    const bine::ShardLaunch &L = ls[l];
+    for (int s = 0; s < L.nten; s++) {
+      const uint64_t k = (uint64_t)L.ten[s], b = shard_bytes[k];
+      for (uint64_t j = 0; j < (uint64_t)nranks; j++) {
+        const uint64_t head =
+            bine::shard_head(bine::shard_dst(dir, packed_addr, block, L.poff[s], flat_addr[k], b, j), b);
+        const uint64_t nvec = bine::seg_nvec(b, head), tail = b - head - 16 * nvec;
+        if (head) put(l, k, j, 0, head, 1);
+        for (uint64_t v = 0; v < nvec; v += bine::kCopyTileVecs)
+          put(l, k, j, head + 16 * v, 16 * std::min<uint64_t>(bine::kCopyTileVecs, nvec - v), 0);
+        if (tail) put(l, k, j, head + 16 * nvec, tail, 1);
+      }
+    }
+  }
+  return nt;
+}
 
 extern "C" int64_t bine_plan_segments(int n, const uint64_t *dst_addr, const uint64_t *src_addr, const size_t *bytes,
                                       uint64_t *out, int64_t cap) {
