@@ -362,6 +362,62 @@ int bine_copy_shards(int n, int nranks, int dir, void *packed, void *const *flat
  * Returns the number of tiles (may exceed cap) or -status. */
 int64_t bine_plan_shards(int n, int nranks, int dir, uint64_t packed_addr, const uint64_t *flat_addr,
                          const size_t *shard_bytes, uint64_t *out, int64_t cap);
+/* ---- sum of squares and clipping of a list of tensors -------------------------
+ * The local halves of a global gradient norm (bine_norm_multi / bine_clip_multi
+ * below).  Element types: BINE_FLOAT, BINE_DOUBLE, BINE_FLOAT16, BINE_BFLOAT16
+ * (the bine_scale_valid(dtype, BINE_SUM) set); any other is BINE_ERR_ARG.
+ *
+ * bine_sumsq_segments: `out` is a device pointer to n + 1 doubles; out[k] = the
+ * sum over i of (double)x_k[i]^2 for k < n, out[n] = out[0] + out[1] + ... +
+ * out[n - 1], added in that order in binary64.  Stream-ordered, no host
+ * synchronization, no allocation.  Every element is converted exactly to
+ * binary64 and squared there (exact for the three narrow types, one rounding
+ * for BINE_DOUBLE); the squares of a segment are added in binary64 in an
+ * order the kernels choose.
+ *   Determinism: the bits of `out` are a function of the data, counts, dtype
+ *     and each buffer's address mod 16 alone -- not of scratch's previous
+ *     contents, earlier calls or the launch's timing (no floating-point
+ *     atomics, no order decided by arrival).
+ *   Accuracy: for finite inputs |out[k] - exact_k| <= counts[k] * 2^-52 *
+ *     exact_k (non-negative terms in any order: relative error at most
+ *     gamma_c ~ c * 2^-53; the factor 2 covers the higher-order terms and, for
+ *     doubles, each square's rounding).  Infinities and NaNs follow IEEE (a NaN
+ *     anywhere in x_k gives NaN in out[k] and out[n]); subnormals are kept.
+ * A segment with counts[k] == 0 gives out[k] = +0.0 and its pointer may be
+ * NULL; n == 0 writes out[0] = +0.0.  `scratch`: at least bine_plan_sumsq(...)
+ * doubles of device memory, one per workgroup of the reduction (one workgroup
+ * per 32 KiB tile of 16-B aligned vectors, at least one per non-empty
+ * segment): k_sumsq_segs stores one partial per workgroup there, k_sumsq_fold
+ * adds a segment's partials (one launch of each per BINE_COPY_SEGS_PER_LAUNCH
+ * non-empty segments, descriptors by value), k_sumsq_total forms out[n].
+ * BINE_SUMSQ_NT=1 in the environment (read at every call) makes k_sumsq_segs'
+ * loads non-temporal: a measurement knob, the bits are the same.
+ * BINE_ERR_ARG, before any HIP call: the dtype; n < 0 or n > BINE_MULTI_MAX; a
+ * NULL array with n > 0; a NULL buffer with a non-zero count; a buffer not
+ * aligned to its element size; out NULL or not 8-byte aligned;
+ * scratch_doubles below bine_plan_sumsq's value, or scratch NULL (or not
+ * 8-byte aligned) when that is non-zero. */
+int bine_sumsq_segments(int n, const void *const *bufs, const size_t *counts, int dtype, double *out,
+                        double *scratch, size_t scratch_doubles, void *stream);
+/* Host only: the doubles of scratch that call needs for these addresses, counts
+ * (elements) and dtype, or -status (the list checks above). */
+int64_t bine_plan_sumsq(int n, const uint64_t *addrs, const size_t *counts, int dtype);
+/* bine_clip_segments: norm2 and coef_out are device pointers to one double
+ * each (coef_out may be NULL; it must not alias norm2).  On the device, in
+ * binary64, every operation correctly rounded:
+ *   r = max_norm / (sqrt(*norm2) + eps),   c = r < 1.0 ? r : 1.0
+ * (so a NaN r -- a NaN *norm2, or 0 / 0 -- gives c = 1.0), then every element
+ * becomes S(x) with scale = c as "scaled reductions" above defines S per type
+ * (BINE_FLOAT: x * (float)c; the 16-bit types: two roundings), in place, and
+ * *coef_out = c.  With c == 1.0 no element's bits change.  One launch of
+ * k_scale_segs per BINE_COPY_SEGS_PER_LAUNCH non-empty segments, descriptors
+ * by value; every workgroup derives c itself from *norm2, so nothing sits
+ * between the norm and the scale, and the call is stream-ordered without host
+ * synchronization.  The segments must not overlap.  BINE_ERR_ARG, before any
+ * HIP call: the list errors of bine_sumsq_segments; norm2 NULL (or norm2 /
+ * coef_out not 8-byte aligned); max_norm or eps negative or NaN. */
+int bine_clip_segments(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
+                       double max_norm, double eps, double *coef_out, void *stream);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -774,6 +830,41 @@ int bine_reduce_scatter_multi(bine_comm_t comm, int algo, int n, const void *con
                               const size_t *shard_counts, int dtype, int op, double scale, int wide, void *stream);
 int bine_allgather_multi(bine_comm_t comm, int algo, int n, const void *const *sbufs, void *const *rbufs,
                          const size_t *shard_counts, int dtype, void *stream);
+/* ---- global norm and clipping of a bucket -------------------------------------
+ * What a sharded training step does after bine_reduce_scatter_multi: the
+ * squared L2 norm of every tensor and of the whole bucket over all ranks, and
+ * one clipping coefficient applied to every shard.  Every rank passes the same
+ * n; counts may differ per rank (shards do).  dtype as bine_sumsq_segments.
+ * bine_norm_multi: `stats` is a device pointer to n + 1 doubles.  With V_r =
+ * what bine_sumsq_segments writes on rank r, stats receives bit for bit what
+ * ONE bine_allreduce returns on V_r: sbuf = BINE_IN_PLACE, count n + 1,
+ * BINE_DOUBLE, BINE_SUM, segsize 0, the same algorithm and communicator
+ * settings.  stats[k] is tensor k's global sum of squares, stats[n] the global
+ * total (the allreduce of the local totals, not a re-sum of stats[0..n)).  A
+ * latency algorithm (BINE_AR_BINE_LAT, BINE_AR_RECURSIVEDOUBLING) is the
+ * intended choice: n + 1 doubles are few, and whatever the single call refuses
+ * (an algorithm that does not take n + 1 < P elements, say) is returned as it
+ * returns it.
+ * Mechanism: V and the reduction's scratch live in the communicator's multi
+ * workspace (bine_allreduce_multi's, grown by its rule), the single call runs
+ * in place there, one bine_copy moves the result to stats; all on the
+ * caller's stream, no host synchronization in steady state.  The kernels of
+ * bine_sumsq_segments / bine_clip_segments are ordinary launches, never
+ * captured; with graph mode on the inner call is captured and replayed as any
+ * call on that address.
+ * bine_clip_multi: stats has n + 2 doubles; bine_norm_multi into stats[0..n],
+ * then bine_clip_segments with norm2 = &stats[n], coef_out = &stats[n + 1]:
+ * every rank scales by the same coefficient bits.
+ * Refusals, before any exchange and any HIP call, in this order: BINE_ERR_ARG
+ * for the dtype; the list checks of bine_sumsq_segments; stats NULL or not
+ * 8-byte aligned; (clip) max_norm or eps negative or NaN; then an algorithm id
+ * outside the allreduce range is BINE_ERR_UNSUPPORTED; then comm == NULL is
+ * BINE_ERR_ARG.  Not provided: norms other than L2, per-tensor coefficients,
+ * mixed element types. */
+int bine_norm_multi(bine_comm_t comm, int algo, int n, const void *const *bufs, const size_t *counts, int dtype,
+                    double *stats, void *stream);
+int bine_clip_multi(bine_comm_t comm, int algo, int n, void *const *bufs, const size_t *counts, int dtype,
+                    double max_norm, double eps, double *stats, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -862,6 +953,13 @@ int bine_loopback_run_reduce_scatter_multi(bine_comm_t *comms, int nranks, int a
 int bine_loopback_run_allgather_multi(bine_comm_t *comms, int nranks, int algo, int n,
                                       const void *const *sbufs, void *const *rbufs, const size_t *shard_counts,
                                       int dtype, int *statuses);
+/* the norm forms: bufs and counts hold nranks * n entries, rank r's tensor k at
+ * [r * n + k]; stats one pointer per rank */
+int bine_loopback_run_norm_multi(bine_comm_t *comms, int nranks, int algo, int n, const void *const *bufs,
+                                 const size_t *counts, int dtype, double *const *stats, int *statuses);
+int bine_loopback_run_clip_multi(bine_comm_t *comms, int nranks, int algo, int n, void *const *bufs,
+                                 const size_t *counts, int dtype, double max_norm, double eps,
+                                 double *const *stats, int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

@@ -35,6 +35,13 @@ shard of EACH tensor of a bucket, ``allgather_multi`` gathers a bucket of shards
 back into the full tensors, each as ONE collective on the rank-major packing.
 ``copy_shards`` is the strided device copy (one descriptor per tensor) between
 the two layouts.
+
+Global norm and clipping: ``norm_multi`` gives every tensor's and the bucket's
+squared L2 norm over all ranks (float64, deterministic bits), ``clip_multi``
+then scales every tensor by min(1, max_norm / (norm + eps)) without a host
+read.  ``sumsq_segments`` and ``clip_segments`` are the local halves: a
+segmented sum of squares and a segmented scale whose factor is read from
+device memory.
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

@@ -181,6 +181,13 @@ def lib():
         "bine_allgather_multi": ([vp, i, i, vp, vp, vp, i, vp], i),
         "bine_loopback_run_reduce_scatter_multi": ([vp, i, i, i, vp, vp, vp, i, i, ctypes.c_double, i, vp], i),
         "bine_loopback_run_allgather_multi": ([vp, i, i, i, vp, vp, vp, i, vp], i),
+        "bine_sumsq_segments": ([i, vp, vp, i, vp, vp, sz, vp], i),
+        "bine_plan_sumsq": ([i, vp, vp, i], ctypes.c_int64),
+        "bine_clip_segments": ([i, vp, vp, i, vp, ctypes.c_double, ctypes.c_double, vp, vp], i),
+        "bine_norm_multi": ([vp, i, i, vp, vp, i, vp, vp], i),
+        "bine_clip_multi": ([vp, i, i, vp, vp, i, ctypes.c_double, ctypes.c_double, vp, vp], i),
+        "bine_loopback_run_norm_multi": ([vp, i, i, i, vp, vp, i, vp, vp], i),
+        "bine_loopback_run_clip_multi": ([vp, i, i, i, vp, vp, i, ctypes.c_double, ctypes.c_double, vp, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

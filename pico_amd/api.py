@@ -651,6 +651,145 @@ def loopback_allgather_multi(comms, algo, sbufs, rbufs, dtype, shard_counts=None
     return rc, list(st)
 
 
+# ---- global norm and clipping of a bucket --------------------------------------------------
+
+def _norm_counts(name: str, bufs, counts):
+    """counts=None: each tensor's numel()"""
+    if counts is None:
+        counts = [b.numel() for b in bufs]
+    if len(counts) != len(bufs):
+        raise ValueError(f"{name}: counts and bufs differ in length")
+    return (ctypes.c_size_t * max(len(counts), 1))(*counts)
+
+
+def _norm_dtype(dtype, bufs) -> int:
+    return dtype if isinstance(dtype, int) else _dtype(dtype, *bufs)
+
+
+def plan_sumsq(addrs: Sequence[int], counts: Sequence[int], dtype) -> int:
+    """The doubles of scratch sumsq_segments needs for these device addresses,
+    element counts and dtype (bine_plan_sumsq, host only): one per workgroup,
+    a workgroup per 32 KiB tile of 16-B aligned vectors and at least one per
+    non-empty tensor."""
+    n = len(counts)
+    if len(addrs) != n:
+        raise ValueError("plan_sumsq: addrs and counts differ in length")
+    r = lib().bine_plan_sumsq(n, (ctypes.c_uint64 * max(n, 1))(*addrs), (ctypes.c_size_t * max(n, 1))(*counts),
+                              _norm_dtype(dtype, ()))
+    if r < 0:
+        raise BineError(int(-r), "bine_plan_sumsq")
+    return int(r)
+
+
+def sumsq_segments(bufs, dtype=None, counts=None, out=None, scratch=None, scratch_doubles=None, stream=None):
+    """out[k] = the sum of tensor k's squares in binary64, out[n] = out[0] + ... +
+    out[n - 1] (bine_sumsq_segments): deterministic bits, relative error at most
+    counts[k] * 2^-52.  float / double / float16 / bfloat16; empty tensors may be
+    None.  `out` (n + 1 float64) and `scratch` (plan_sumsq(...) float64; a raw
+    address needs scratch_doubles) are allocated with torch when not given.
+    Returns out."""
+    n = len(bufs)
+    c = _norm_counts("sumsq_segments", bufs, counts)
+    dt = _norm_dtype(dtype, bufs)
+    if out is None or scratch is None:
+        import torch
+        dev = next((b.device for b in bufs if hasattr(b, "device")), "cuda")
+        if out is None:
+            out = torch.empty(n + 1, dtype=torch.float64, device=dev)
+        if scratch is None:
+            need = plan_sumsq([_ptr(b) or 0 for b in bufs], list(c)[:n], dt)
+            scratch = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
+    if scratch_doubles is None:
+        scratch_doubles = scratch.numel() if hasattr(scratch, "numel") else 0
+    check(lib().bine_sumsq_segments(n, _ptrs(bufs), c, dt, _ptr(out), _ptr(scratch), scratch_doubles,
+                                    _stream(stream, None)), "bine_sumsq_segments")
+    return out
+
+
+def clip_segments(bufs, norm2, max_norm: float, eps: float = 0.0, dtype=None, counts=None, coef_out=None,
+                  stream=None) -> None:
+    """Every tensor scaled in place by c = min(1, max_norm / (sqrt(norm2[0]) +
+    eps)), computed on the device in binary64 from the device double `norm2`
+    (bine_clip_segments); coef_out (a device double, optional) receives c.
+    The multiplication is scale()'s, per element type; c == 1 changes nothing."""
+    c = _norm_counts("clip_segments", bufs, counts)
+    check(lib().bine_clip_segments(len(bufs), _ptrs(bufs), c, _norm_dtype(dtype, bufs), _ptr(norm2), float(max_norm),
+                                   float(eps), _ptr(coef_out), _stream(stream, None)), "bine_clip_segments")
+
+
+def _stats(bufs, stats, extra: int):
+    if stats is None:
+        import torch
+        dev = next((b.device for b in bufs if hasattr(b, "device")), "cuda")
+        stats = torch.empty(len(bufs) + extra, dtype=torch.float64, device=dev)
+    return stats
+
+
+def norm_multi(algo, bufs, dtype, comm: Comm, counts=None, stats=None, stream=None):
+    """bine_norm_multi: stats[k] = tensor k's sum of squares over all ranks,
+    stats[n] = the bucket's -- bit for bit ONE in-place allreduce (double, sum)
+    of the ranks' sumsq_segments vectors.  Every rank passes the same number of
+    tensors; counts may differ per rank.  A latency algorithm ("bine_lat",
+    "recursivedoubling") is the intended choice.  stats: n + 1 float64 on the
+    device (allocated when None).  Returns stats."""
+    stats = _stats(bufs, stats, 1)
+    c = _norm_counts("norm_multi", bufs, counts)
+    check(lib().bine_norm_multi(comm.handle, _algo("allreduce", algo), len(bufs), _ptrs(bufs), c,
+                                _norm_dtype(dtype, bufs), _ptr(stats), _stream(stream, comm)),
+          f"norm_multi ({algo})")
+    return stats
+
+
+def clip_multi(algo, bufs, dtype, comm: Comm, max_norm: float, eps: float = 0.0, counts=None, stats=None,
+               stream=None):
+    """bine_clip_multi: norm_multi into stats[0..n], then every tensor scaled in
+    place by c = min(1, max_norm / (sqrt(stats[n]) + eps)) (clip_segments);
+    stats[n + 1] = c, the same bits on every rank.  stats: n + 2 float64.
+    Returns stats."""
+    stats = _stats(bufs, stats, 2)
+    c = _norm_counts("clip_multi", bufs, counts)
+    check(lib().bine_clip_multi(comm.handle, _algo("allreduce", algo), len(bufs), _ptrs(bufs), c,
+                                _norm_dtype(dtype, bufs), float(max_norm), float(eps), _ptr(stats),
+                                _stream(stream, comm)), f"clip_multi ({algo})")
+    return stats
+
+
+def _loopback_norm(name: str, bufs, stats, counts):
+    n = len(bufs[0])
+    if any(len(b) != n for b in bufs) or len(stats) != len(bufs):
+        raise ValueError(f"{name}: the ranks' lists differ in length")
+    if counts is None:
+        counts = [[b.numel() for b in r] for r in bufs]
+    if len(counts) != len(bufs) or any(len(c) != n for c in counts):
+        raise ValueError(f"{name}: counts and bufs differ in length")
+    flat = [b for r in bufs for b in r]
+    flat_c = [c for r in counts for c in r]
+    return n, flat, (ctypes.c_size_t * max(len(flat_c), 1))(*flat_c)
+
+
+def loopback_norm_multi(comms, algo, bufs, dtype, stats, counts=None):
+    """bufs: one list of tensors per virtual rank; counts likewise (None: each
+    tensor's numel()); stats: one device float64 buffer of n + 1 per rank.
+    Returns (status, per-rank statuses)."""
+    st = (ctypes.c_int * len(comms))()
+    hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
+    n, flat, c = _loopback_norm("loopback_norm_multi", bufs, stats, counts)
+    rc = lib().bine_loopback_run_norm_multi(hs, len(comms), _algo("allreduce", algo), n, _ptrs(flat), c,
+                                            _norm_dtype(dtype, flat), _ptrs(stats), st)
+    return rc, list(st)
+
+
+def loopback_clip_multi(comms, algo, bufs, dtype, max_norm, eps, stats, counts=None):
+    """as loopback_norm_multi, clip_multi on every virtual rank; stats: n + 2
+    float64 per rank."""
+    st = (ctypes.c_int * len(comms))()
+    hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
+    n, flat, c = _loopback_norm("loopback_clip_multi", bufs, stats, counts)
+    rc = lib().bine_loopback_run_clip_multi(hs, len(comms), _algo("allreduce", algo), n, _ptrs(flat), c,
+                                            _norm_dtype(dtype, flat), float(max_norm), float(eps), _ptrs(stats), st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -1041,6 +1180,8 @@ __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fus
            "wide_plan", "copy_segments", "plan_segments", "allreduce_multi", "loopback_allreduce_multi",
            "copy_shards", "plan_shards", "reduce_scatter_multi", "allgather_multi",
            "loopback_reduce_scatter_multi", "loopback_allgather_multi",
+           "sumsq_segments", "plan_sumsq", "clip_segments", "norm_multi", "clip_multi", "loopback_norm_multi",
+           "loopback_clip_multi",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

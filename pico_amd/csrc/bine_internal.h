@@ -253,6 +253,37 @@ int plan_shard_launches(int n, int nranks, int dir, uint64_t packed_addr, const 
                         const size_t *bytes, std::vector<ShardLaunch> &out, uint64_t *block_bytes);
 int launch_copy_shards(int n, int nranks, int dir, void *packed, void *const *flat, const size_t *bytes,
                        void *stream);
+// segmented sum of squares and segmented scale (bine_sumsq_segments /
+// bine_clip_segments): both walk the segmented copy's tile table with
+// destination = source = the buffer, so a tile is up to kCopyTileVecs 16-B
+// ALIGNED vectors of whole elements and a segment's first workgroup also takes
+// the elements before the first and after the last vector.
+// norm_esz: the element size of the four types the two calls take, 0 otherwise.
+size_t norm_esz(int dtype);
+// The checks of a list that need no device, in the header's order (dtype, n, a
+// NULL array, a NULL buffer with a non-zero count, a buffer not aligned to its
+// element), then the launches and their workgroups summed over the launches
+// (`tiles`: the doubles of scratch bine_sumsq_segments needs).  BINE_SUCCESS or
+// BINE_ERR_ARG.
+int plan_norm_launches(int n, const uint64_t *addrs, const size_t *counts, int dtype, std::vector<SegLaunch> &out,
+                       uint64_t *tiles);
+// k_sumsq_segs per launch of `ls` (one double per workgroup into `scratch`, the
+// launches' workgroups one after another); the opset-0 entry forwards the
+// 16-bit types.  nt: non-temporal loads.
+int launch_sumsq_tiles(const std::vector<SegLaunch> &ls, const void *const *bufs, const size_t *counts, int dtype,
+                       double *scratch, bool nt, void *stream);
+int launch_sumsq_tiles_h16(const std::vector<SegLaunch> &ls, const void *const *bufs, const size_t *counts,
+                           int dtype, double *scratch, bool nt, void *stream);
+// bine_sumsq_segments: the checks, launch_sumsq_tiles, then k_sumsq_fold per
+// launch (a segment's partials -> out[k]) and one k_sumsq_total (the empty
+// segments' zeros and out[n])
+int launch_sumsq_segments(int n, const void *const *bufs, const size_t *counts, int dtype, double *out,
+                          double *scratch, size_t scratch_doubles, void *stream);
+// bine_clip_segments: k_scale_segs per launch of the same table, in place
+int launch_clip_segments(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
+                         double max_norm, double eps, double *coef_out, void *stream);
+int launch_clip_segments_h16(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
+                             double max_norm, double eps, double *coef_out, void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -2049,6 +2049,16 @@ int bine_copy_shards(int n, int nranks, int dir, void *packed, void *const *flat
   return launch_copy_shards(n, nranks, dir, packed, flat, shard_bytes, stream);  // likewise
 }
 
+int bine_sumsq_segments(int n, const void *const *bufs, const size_t *counts, int dtype, double *out, double *scratch,
+                        size_t scratch_doubles, void *stream) {
+  return launch_sumsq_segments(n, bufs, counts, dtype, out, scratch, scratch_doubles, stream);  // checks its arguments
+}
+
+int bine_clip_segments(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
+                       double max_norm, double eps, double *coef_out, void *stream) {
+  return launch_clip_segments(n, bufs, counts, dtype, norm2, max_norm, eps, coef_out, stream);  // likewise
+}
+
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream) {
   return launch_fill_pico(buf, count, dtype, seed, stream);
 }
@@ -2630,6 +2640,57 @@ int bine_allgather_multi(bine_comm_t c, int algo, int n, const void *const *sbuf
   return launch_copy_shards(n, (int)P, 1, recv, rbufs, bytes.data(), K);
 }
 
+// ---- global norm and clipping of a bucket (bine_amd.h) -----------------------------------
+
+// the checks that need no communicator, in the header's order; clip: max_norm
+// and eps too (before the algorithm id: before any exchange)
+static int norm_args(int algo, int n, const void *const *bufs, const size_t *counts, int dtype, const double *stats,
+                     bool clip, double max_norm, double eps, uint64_t *tiles = nullptr) {
+  if (!norm_esz(dtype)) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!bufs || !counts))) return BINE_ERR_ARG;
+  uint64_t addr[BINE_MULTI_MAX];
+  for (int k = 0; k < n; k++) addr[k] = (uint64_t)(uintptr_t)bufs[k];
+  std::vector<SegLaunch> ls;
+  if (const int rc = plan_norm_launches(n, addr, counts, dtype, ls, tiles)) return rc;
+  if (!stats || ((uintptr_t)stats & 7)) return BINE_ERR_ARG;
+  if (clip && (!(max_norm >= 0.0) || !(eps >= 0.0))) return BINE_ERR_ARG;  // negative or NaN
+  if (algo < BINE_AR_RECURSIVEDOUBLING || algo > BINE_AR_BINE_BLOCK_BY_BLOCK_ANY_EVEN) return BINE_ERR_UNSUPPORTED;
+  return BINE_SUCCESS;
+}
+
+// V (n + 1 doubles) and the tile partials live in the multi workspace; the
+// single allreduce runs in place on V; one bine_copy moves it to stats
+static int norm_run(bine_comm_t c, int algo, int n, const void *const *bufs, const size_t *counts, int dtype,
+                    uint64_t tiles, double *stats, void *stream) {
+  if (!c) return BINE_ERR_ARG;
+  hipStream_t K = (hipStream_t)stream;
+  const size_t vbytes = (((size_t)n + 1) * sizeof(double) + 255) & ~(size_t)255;
+  const size_t need = vbytes + (((size_t)tiles * sizeof(double) + 255) & ~(size_t)255);
+  char *ws;
+  if (const int rc = multi_workspace(c, need, K, &ws)) return rc;
+  double *V = (double *)ws, *scratch = (double *)(ws + vbytes);
+  int rc = launch_sumsq_segments(n, bufs, counts, dtype, V, scratch, (size_t)tiles, K);
+  if (rc) return rc;
+  rc = bine_allreduce(c, algo, BINE_IN_PLACE, V, (size_t)n + 1, BINE_DOUBLE, BINE_SUM, 0, K);
+  if (rc) return rc;
+  return launch_copy(stats, V, ((size_t)n + 1) * sizeof(double), K);
+}
+
+int bine_norm_multi(bine_comm_t c, int algo, int n, const void *const *bufs, const size_t *counts, int dtype,
+                    double *stats, void *stream) {
+  uint64_t tiles = 0;
+  if (const int rc = norm_args(algo, n, bufs, counts, dtype, stats, false, 0.0, 0.0, &tiles)) return rc;
+  return norm_run(c, algo, n, bufs, counts, dtype, tiles, stats, stream);
+}
+
+int bine_clip_multi(bine_comm_t c, int algo, int n, void *const *bufs, const size_t *counts, int dtype,
+                    double max_norm, double eps, double *stats, void *stream) {
+  uint64_t tiles = 0;
+  if (const int rc = norm_args(algo, n, bufs, counts, dtype, stats, true, max_norm, eps, &tiles)) return rc;
+  if (const int rc = norm_run(c, algo, n, bufs, counts, dtype, tiles, stats, stream)) return rc;
+  return launch_clip_segments(n, bufs, counts, dtype, stats + n, max_norm, eps, stats + n + 1, stream);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -2900,6 +2961,41 @@ int bine_loopback_run_allgather_multi(bine_comm_t *comms, int nranks, int algo, 
     (void)hipSetDevice(comms[r]->device);
     return bine_allgather_multi(comms[r], algo, n, sb(r), rb(r), shard_counts, dtype, comms[r]->stream);
   });
+}
+
+// bufs and counts: nranks * n entries, rank r's tensor k at [r * n + k]; stats:
+// one pointer per rank
+static int loopback_norm(bool clip, bine_comm_t *comms, int nranks, int algo, int n, void *const *bufs,
+                         const size_t *counts, int dtype, double max_norm, double eps, double *const *stats,
+                         int *statuses) {
+  // before any thread, stream or HIP call: what a rank would refuse without a communicator
+  auto bf = [&](int r) { return bufs && n > 0 ? bufs + (size_t)r * n : bufs; };
+  auto ct = [&](int r) { return counts && n > 0 ? counts + (size_t)r * n : counts; };
+  int bad = BINE_SUCCESS;
+  for (int r = 0; !bad && r < nranks; r++)
+    bad = norm_args(algo, n, bf(r), ct(r), dtype, stats ? stats[r] : nullptr, clip, max_norm, eps);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return bad;
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    if (clip)
+      return bine_clip_multi(comms[r], algo, n, bf(r), ct(r), dtype, max_norm, eps, stats[r], comms[r]->stream);
+    return bine_norm_multi(comms[r], algo, n, bf(r), ct(r), dtype, stats[r], comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_norm_multi(bine_comm_t *comms, int nranks, int algo, int n, const void *const *bufs,
+                                 const size_t *counts, int dtype, double *const *stats, int *statuses) {
+  return loopback_norm(false, comms, nranks, algo, n, const_cast<void *const *>(bufs), counts, dtype, 0.0, 0.0, stats,
+                       statuses);
+}
+
+int bine_loopback_run_clip_multi(bine_comm_t *comms, int nranks, int algo, int n, void *const *bufs,
+                                 const size_t *counts, int dtype, double max_norm, double eps, double *const *stats,
+                                 int *statuses) {
+  return loopback_norm(true, comms, nranks, algo, n, bufs, counts, dtype, max_norm, eps, stats, statuses);
 }
 
 int bine_loopback_run_reduce_scatter_wide(bine_comm_t *comms, int n, int algo, const void *const *sbufs,

@@ -1323,6 +1323,333 @@ int BINE_FN(launch_scale)(const void *in, void *out, size_t count, int dtype, do
     else return BINE_ERR_ARG;
   });
 }
+
+// ----------------------------------------------------------------------------
+// segmented sum of squares and segmented scale (bine_sumsq_segments /
+// bine_clip_segments: the global gradient norm and the clipping of a bucket).
+// Both take k_copy_segs' dispatch -- up to kSegsPerLaunch descriptors by value,
+// the grid the concatenation of the segments' tiles, a binary search over the
+// tile prefix -- over the table plan_seg_launches builds with destination =
+// source = the buffer (plan_norm_launches): a tile is kBlock * kScaleU 16-B
+// aligned vectors of whole elements, and a segment's first workgroup also
+// takes the elements before the first and after the last vector.
+static_assert(kCopyTileVecs == (uint64_t)kBlock * kScaleU, "the planner's tile is k_scale's");
+
+struct NormSeg {
+  uint8_t *p;
+  uint64_t bytes;
+};
+
+// tile0[k] <= t < tile0[k + 1], nseg >= 1 (workgroup-uniform: scalar loads)
+__device__ __forceinline__ uint32_t seg_of_tile(const uint32_t *tile0, uint32_t nseg, uint32_t t) {
+  uint32_t k = 0, hi = nseg;
+  while (hi - k > 1) {
+    const uint32_t mid = (k + hi) >> 1;
+    if (t >= tile0[mid]) k = mid;
+    else hi = mid;
+  }
+  return k;
+}
+
+// The workgroup's sum of one double per lane, in an order fixed by the lane
+// numbers alone: the 64 lanes of a wave by a butterfly of __shfl_xor (both
+// partners add the same two values, so every lane holds the same bits), the
+// waves through LDS in wave order.  Valid in every thread.
+__device__ __forceinline__ double wg_sum(double v, double *part) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = part[0];
+#pragma unroll
+  for (int w = 1; w < kBlock / 64; w++) s += part[w];
+  return s;
+}
+
+// x widened exactly to binary64 and squared there (exact for the three narrow
+// types: at most 24-bit significands; one rounding for double)
+template <typename T>
+__device__ __forceinline__ double sq64(T x) {
+  const double d = (double)x;
+  return d * d;
+}
+// the squares of one 16-B vector's elements, added in element order
+template <typename T>
+__device__ __forceinline__ double sumsq16(u32x4 v) {
+  constexpr int N = 16 / (int)sizeof(T);
+  T e[N];
+  __builtin_memcpy(e, &v, 16);
+  double s = sq64<T>(e[0]);
+#pragma unroll
+  for (int i = 1; i < N; i++) s += sq64<T>(e[i]);
+  return s;
+}
+
+// k_sumsq_segs: workgroup t stores the sum of squares of its tile to
+// scratch[t].  Every load is issued before the first use; a lane adds its
+// vectors' sums in vector order, wg_sum combines the lanes.  No atomics, no
+// order decided by arrival: the bits depend on the data, the counts, the type
+// and the buffers' addresses mod 16 B alone.
+struct SumsqSegs {
+  uint32_t nseg;
+  uint32_t tile0[kSegsPerLaunch + 1];
+  double *scratch;  // this launch's first workgroup's double
+  NormSeg s[kSegsPerLaunch];
+};
+static_assert(sizeof(SumsqSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+
+template <typename T, bool NT>
+__global__ __launch_bounds__(kBlock) void k_sumsq_segs(SumsqSegs a) {
+  __shared__ double part[kBlock / 64];
+  const uint32_t t = blockIdx.x, k = seg_of_tile(a.tile0, a.nseg, t), wt = t - a.tile0[k];
+  const uint8_t *p = a.s[k].p;
+  const size_t n = a.s[k].bytes;
+  const size_t h = (16 - ((uintptr_t)p & 15)) & 15, head = h < n ? h : n, nvec = (n - head) / 16;
+  double acc = 0.0;
+  if (wt == 0) {  // head and tail elements of this segment
+    const T *e = reinterpret_cast<const T *>(p);
+    const size_t ne = n / sizeof(T), he = head / sizeof(T), te = (head + nvec * 16) / sizeof(T);
+    for (size_t i = threadIdx.x; i < he; i += kBlock) acc += sq64<T>(e[i]);
+    for (size_t i = te + threadIdx.x; i < ne; i += kBlock) acc += sq64<T>(e[i]);
+  }
+  const u32x4 *vs = reinterpret_cast<const u32x4 *>(p + head);
+  const size_t base = (size_t)wt * kBlock * kScaleU + threadIdx.x;
+  if (base + (kScaleU - 1) * (size_t)kBlock < nvec) {
+    u32x4 x[kScaleU];
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) x[u] = ld<NT>(vs + base + (size_t)u * kBlock);
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) acc += sumsq16<T>(x[u]);
+  } else {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if (i < nvec) acc += sumsq16<T>(ld<NT>(vs + i));
+    }
+  }
+  acc = wg_sum(acc, part);
+  if (threadIdx.x == 0) a.scratch[t] = acc;
+}
+
+int BINE_FN(launch_sumsq_tiles)(const std::vector<SegLaunch> &ls, const void *const *bufs, const size_t *counts,
+                                int dtype, double *scratch, bool nt, void *stream) {
+#if BINE_OPSET == 0
+  if (h16_dtype(dtype)) return launch_sumsq_tiles_h16(ls, bufs, counts, dtype, scratch, nt, stream);
+#endif
+  hipStream_t st = (hipStream_t)stream;
+  return with_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    if constexpr (kScaleT<T>) {
+      uint64_t t0 = 0;
+      for (const SegLaunch &L : ls) {
+        SumsqSegs a;
+        a.nseg = (uint32_t)L.nseg;
+        a.scratch = scratch + t0;
+        for (int s = 0; s < L.nseg; s++) {
+          a.tile0[s] = L.tile0[s];
+          a.s[s] = {(uint8_t *)const_cast<void *>(bufs[L.seg[s]]), (uint64_t)(counts[L.seg[s]] * sizeof(T))};
+        }
+        for (int s = L.nseg; s <= kSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nseg];
+        for (int s = L.nseg; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, 0};
+        if (nt) hipLaunchKernelGGL((k_sumsq_segs<T, true>), dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((k_sumsq_segs<T, false>), dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
+        if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+        t0 += L.tile0[L.nseg];
+      }
+      return BINE_SUCCESS;
+    } else return BINE_ERR_ARG;
+  });
+}
+
+#if BINE_OPSET == 0
+// k_sumsq_fold: workgroup s adds the partials of the launch's s-th segment --
+// lane l takes partials l, l + kBlock, ... in index order, wg_sum combines the
+// lanes -- and stores out[seg[s]].  k_sumsq_total: the empty segments' +0.0,
+// then out[n] = out[0] + ... + out[n - 1], added in that order by one thread
+// out of LDS.
+struct SumsqFold {
+  uint32_t tile0[kSegsPerLaunch + 1];
+  uint16_t seg[kSegsPerLaunch];
+  const double *scratch;  // this launch's first workgroup's double
+  double *out;
+};
+struct SumsqTotal {
+  int n;
+  uint32_t empty[BINE_MULTI_MAX / 32];  // bit k: segment k has no element
+  double *out;
+};
+static_assert(BINE_MULTI_MAX % 32 == 0 && BINE_MULTI_MAX <= 65536, "SumsqTotal::empty, SumsqFold::seg");
+
+__global__ __launch_bounds__(kBlock) void k_sumsq_fold(SumsqFold a) {
+  __shared__ double part[kBlock / 64];
+  const uint32_t s = blockIdx.x, hi = a.tile0[s + 1];
+  double acc = 0.0;
+  for (uint32_t i = a.tile0[s] + threadIdx.x; i < hi; i += kBlock) acc += a.scratch[i];
+  acc = wg_sum(acc, part);
+  if (threadIdx.x == 0) a.out[a.seg[s]] = acc;
+}
+
+__global__ __launch_bounds__(kBlock) void k_sumsq_total(SumsqTotal a) {
+  __shared__ double v[BINE_MULTI_MAX];
+  for (int k = threadIdx.x; k < a.n; k += kBlock) {
+    const bool empty = (a.empty[k >> 5] >> (k & 31)) & 1;
+    if (empty) a.out[k] = 0.0;
+    v[k] = empty ? 0.0 : a.out[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < a.n; k++) s += v[k];
+    a.out[a.n] = s;
+  }
+}
+
+// BINE_SUMSQ_NT in the environment (read at every call): 1 / 0 = non-temporal
+// / plain loads in k_sumsq_segs; unset: plain
+static bool sumsq_nt() {
+  const char *e = getenv("BINE_SUMSQ_NT");
+  return e && *e == '1';
+}
+
+int launch_sumsq_segments(int n, const void *const *bufs, const size_t *counts, int dtype, double *out,
+                          double *scratch, size_t scratch_doubles, void *stream) {
+  if (!norm_esz(dtype)) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!bufs || !counts))) return BINE_ERR_ARG;
+  uint64_t addr[BINE_MULTI_MAX];
+  for (int k = 0; k < n; k++) addr[k] = (uint64_t)(uintptr_t)bufs[k];
+  std::vector<SegLaunch> ls;
+  uint64_t tiles = 0;
+  if (const int rc = plan_norm_launches(n, addr, counts, dtype, ls, &tiles)) return rc;
+  if (!out || ((uintptr_t)out & 7)) return BINE_ERR_ARG;
+  if (scratch_doubles < tiles || (tiles && (!scratch || ((uintptr_t)scratch & 7)))) return BINE_ERR_ARG;
+  if (const int rc = launch_sumsq_tiles(ls, bufs, counts, dtype, scratch, sumsq_nt(), stream)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t t0 = 0;
+  for (const SegLaunch &L : ls) {
+    SumsqFold f;
+    for (int s = 0; s <= kSegsPerLaunch; s++) f.tile0[s] = L.tile0[s < L.nseg ? s : L.nseg];
+    for (int s = 0; s < kSegsPerLaunch; s++) f.seg[s] = (uint16_t)(s < L.nseg ? L.seg[s] : 0);
+    f.scratch = scratch + t0;
+    f.out = out;
+    hipLaunchKernelGGL(k_sumsq_fold, dim3((unsigned)L.nseg), dim3(kBlock), 0, st, f);
+    if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+    t0 += L.tile0[L.nseg];
+  }
+  SumsqTotal tot;
+  tot.n = n;
+  tot.out = out;
+  memset(tot.empty, 0, sizeof tot.empty);
+  for (int k = 0; k < n; k++)
+    if (!counts[k]) tot.empty[k >> 5] |= 1u << (k & 31);
+  hipLaunchKernelGGL(k_sumsq_total, dim3(1), dim3(kBlock), 0, st, tot);
+  return hipGetLastError() == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
+}
+#endif  // BINE_OPSET == 0
+
+// k_scale_segs: k_scale's in-place tile body on tile t's segment, the factor
+// read from device memory.  Every workgroup derives the coefficient itself
+// (one binary64 square root and one division, both IEEE: no fast-math),
+//   r = max_norm / (sqrt(*norm2) + eps),  c = r < 1.0 ? r : 1.0,
+// so no launch sits between the norm and the scale; the first workgroup stores
+// it to *coef_out.  c == 1.0: nothing is stored.  A full tile's loads are
+// issued before the coefficient's arithmetic, which so overlaps them.
+struct ScaleSegs {
+  uint32_t nseg;  // 0: the launch only stores the coefficient
+  uint32_t tile0[kSegsPerLaunch + 1];
+  const double *norm2;
+  double *coef_out;  // NULL: not stored
+  double max_norm, eps;
+  NormSeg s[kSegsPerLaunch];
+};
+static_assert(sizeof(ScaleSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+
+__device__ __forceinline__ double clip_coef(const ScaleSegs &a) {
+  const double r = a.max_norm / (__builtin_sqrt(*a.norm2) + a.eps);
+  return r < 1.0 ? r : 1.0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_scale_segs(ScaleSegs a) {
+  constexpr size_t V = 16 / sizeof(T);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && a.coef_out) *a.coef_out = clip_coef(a);
+  if (a.nseg == 0) return;
+  const uint32_t t = blockIdx.x, k = seg_of_tile(a.tile0, a.nseg, t), wt = t - a.tile0[k];
+  uint8_t *p = a.s[k].p;
+  const size_t n = a.s[k].bytes;
+  const size_t h = (16 - ((uintptr_t)p & 15)) & 15, head = h < n ? h : n, nvec = (n - head) / 16;
+  u32x4 *vd = reinterpret_cast<u32x4 *>(p + head);
+  const size_t base = (size_t)wt * kBlock * kScaleU + threadIdx.x;
+  const bool full = base + (kScaleU - 1) * (size_t)kBlock < nvec;
+  u32x4 x[kScaleU];
+  if (full) {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) x[u] = vd[base + (size_t)u * kBlock];
+  }
+  const double c = clip_coef(a);
+  if (c == 1.0) return;
+  const mul_of<T> m = (mul_of<T>)c;  // (float)c: round to nearest even, as bine_scale's host conversion
+  if (wt == 0) {  // head and tail elements of this segment
+    T *e = reinterpret_cast<T *>(p);
+    const size_t ne = n / sizeof(T), he = head / sizeof(T);
+    for (size_t i = threadIdx.x; i < he; i += kBlock) e[i] = scale1<T>(e[i], m);
+    for (size_t i = he + nvec * V + threadIdx.x; i < ne; i += kBlock) e[i] = scale1<T>(e[i], m);
+  }
+  if (full) {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++)
+      __builtin_nontemporal_store(scale16<T>(x[u], m), vd + base + (size_t)u * kBlock);
+  } else {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if (i < nvec) vd[i] = scale16<T>(vd[i], m);
+    }
+  }
+}
+
+int BINE_FN(launch_clip_segments)(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
+                                  double max_norm, double eps, double *coef_out, void *stream) {
+  if (!norm_esz(dtype)) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!bufs || !counts))) return BINE_ERR_ARG;
+#if BINE_OPSET == 0
+  if (h16_dtype(dtype))
+    return launch_clip_segments_h16(n, bufs, counts, dtype, norm2, max_norm, eps, coef_out, stream);
+#endif
+  uint64_t addr[BINE_MULTI_MAX];
+  for (int k = 0; k < n; k++) addr[k] = (uint64_t)(uintptr_t)bufs[k];
+  std::vector<SegLaunch> ls;
+  if (const int rc = plan_norm_launches(n, addr, counts, dtype, ls, nullptr)) return rc;
+  if (!norm2 || ((uintptr_t)norm2 & 7) || ((uintptr_t)coef_out & 7)) return BINE_ERR_ARG;
+  if (!(max_norm >= 0.0) || !(eps >= 0.0)) return BINE_ERR_ARG;  // negative or NaN
+  hipStream_t st = (hipStream_t)stream;
+  return with_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    if constexpr (kScaleT<T>) {
+      ScaleSegs a;
+      a.norm2 = norm2, a.coef_out = coef_out, a.max_norm = max_norm, a.eps = eps;
+      if (ls.empty()) {  // nothing to scale: the coefficient alone
+        if (!coef_out) return BINE_SUCCESS;
+        a.nseg = 0;
+        for (int s = 0; s <= kSegsPerLaunch; s++) a.tile0[s] = 0;
+        for (int s = 0; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, 0};
+        hipLaunchKernelGGL((k_scale_segs<T>), dim3(1), dim3(kBlock), 0, st, a);
+        return status(hipGetLastError());
+      }
+      for (const SegLaunch &L : ls) {
+        a.nseg = (uint32_t)L.nseg;
+        for (int s = 0; s < L.nseg; s++) {
+          a.tile0[s] = L.tile0[s];
+          a.s[s] = {(uint8_t *)bufs[L.seg[s]], (uint64_t)(counts[L.seg[s]] * sizeof(T))};
+        }
+        for (int s = L.nseg; s <= kSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nseg];
+        for (int s = L.nseg; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, 0};
+        hipLaunchKernelGGL((k_scale_segs<T>), dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
+        if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+        a.coef_out = nullptr;  // stored once, by the first launch
+      }
+      return BINE_SUCCESS;
+    } else return BINE_ERR_ARG;
+  });
+}
 #endif  // BINE_OPSET != 1
 
 #if BINE_OPSET == 2

@@ -8,7 +8,10 @@
 // k_copy_segs derives a segment's head and vector count from the same two
 // expressions (seg_head / seg_nvec) over the same descriptor.  The sharded
 // copy is built the same way: plan_shard_launches / bine_plan_shards are what
-// launch_copy_shards issues as k_copy_shards (tools/shards_check.cpp).
+// launch_copy_shards issues as k_copy_shards (tools/shards_check.cpp).  The
+// segmented sum of squares and the segmented scale walk plan_seg_launches'
+// table over the buffers themselves: plan_norm_launches / bine_plan_sumsq
+// (tools/sumsq_check.cpp).
 #include <algorithm>
 
 #include "bine_internal.h"
@@ -97,7 +100,47 @@ int plan_shard_launches(int n, int nranks, int dir, uint64_t packed_addr, const 
   return BINE_SUCCESS;
 }
 
+size_t norm_esz(int dtype) {
+  switch (dtype) {
+    case BINE_FLOAT: return 4;
+    case BINE_DOUBLE: return 8;
+    case BINE_FLOAT16:
+    case BINE_BFLOAT16: return 2;
+    default: return 0;
+  }
+}
+
+int plan_norm_launches(int n, const uint64_t *addrs, const size_t *counts, int dtype, std::vector<SegLaunch> &out,
+                       uint64_t *tiles) {
+  out.clear();
+  if (tiles) *tiles = 0;
+  const size_t esz = norm_esz(dtype);
+  if (!esz) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX) return BINE_ERR_ARG;
+  if (n > 0 && (!addrs || !counts)) return BINE_ERR_ARG;
+  for (int k = 0; k < n; k++)
+    if (counts[k] && !addrs[k]) return BINE_ERR_ARG;
+  std::vector<size_t> bytes((size_t)n);
+  for (int k = 0; k < n; k++) {
+    if (counts[k] && addrs[k] % esz) return BINE_ERR_ARG;
+    if (counts[k] > ((size_t)1 << 56)) return BINE_ERR_ARG;  // keeps the byte count and every sum below 2^64
+    bytes[k] = counts[k] * esz;
+  }
+  if (const int rc = plan_seg_launches(n, addrs, addrs, bytes.data(), out)) return rc;
+  uint64_t t = 0;
+  for (const SegLaunch &L : out) t += L.tile0[L.nseg];
+  if (tiles) *tiles = t;
+  return BINE_SUCCESS;
+}
+
 }  // namespace bine
+
+extern "C" int64_t bine_plan_sumsq(int n, const uint64_t *addrs, const size_t *counts, int dtype) {
+  std::vector<bine::SegLaunch> ls;
+  uint64_t tiles = 0;
+  const int rc = bine::plan_norm_launches(n, addrs, counts, dtype, ls, &tiles);
+  return rc ? -(int64_t)rc : (int64_t)tiles;
+}
 
 extern "C" int64_t bine_plan_shards(int n, int nranks, int dir, uint64_t packed_addr, const uint64_t *flat_addr,
                                     const size_t *shard_bytes, uint64_t *out, int64_t cap) {
