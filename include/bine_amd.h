@@ -418,6 +418,75 @@ int64_t bine_plan_sumsq(int n, const uint64_t *addrs, const size_t *counts, int 
  * coef_out not 8-byte aligned); max_norm or eps negative or NaN. */
 int bine_clip_segments(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
                        double max_norm, double eps, double *coef_out, void *stream);
+/* ---- fused AdamW step over a list of shards -----------------------------------
+ * What a sharded training step does between bine_clip_multi and
+ * bine_allgather_multi (bine_adamw_multi below): one decoupled-weight-decay
+ * Adam update of every shard in one pass -- the gradient read once and never
+ * rewritten, the clip coefficient read from device memory, the 16-bit copy of
+ * the new parameter stored where the allgather wants it.
+ *
+ * bine_adamw_consts (host only): the step's eight constants, each computed in
+ * binary64 and rounded once to binary32 (nearest even):
+ *   out[0] dk   = 1 - lr * weight_decay      out[4] omb2 = 1 - beta2
+ *   out[1] b1   = beta1                      out[5] rbc2 = 1 / sqrt(1 - beta2^step)
+ *   out[2] omb1 = 1 - beta1                  out[6] eps
+ *   out[3] b2   = beta2                      out[7] ss   = lr / (1 - beta1^step)
+ * BINE_ERR_ARG: lr, eps or weight_decay negative or NaN; a beta outside [0, 1)
+ * or NaN; step < 1; out NULL.  Every entry point below derives its constants
+ * through this function and nothing else.
+ *
+ * bine_adamw_segments: p, m, v are binary32 and updated in place; g has gdtype
+ * and is read only; pout may be NULL as a whole, otherwise it has odtype and is
+ * written only (gdtype, odtype: BINE_FLOAT, BINE_FLOAT16 or BINE_BFLOAT16;
+ * odtype is checked even without pout).  gcoef: a device pointer to one
+ * double, NULL meaning 1.0 (intended: bine_clip_multi's &stats[n + 1]);
+ * grad_mul: a host double, 1 / loss scale say.  Per element, every line one
+ * correctly rounded binary32 operation, nothing contracted, subnormals kept:
+ *   gm = (float)(c * grad_mul)          c = gcoef ? *gcoef : 1.0; the product in
+ *                                       binary64, one rounding to binary32
+ *   gs = widen(g) * gm                  widen exact
+ *   p1 = p * dk
+ *   m' = (m * b1) + (gs * omb1)
+ *   v' = (v * b2) + ((gs * gs) * omb2)
+ *   d  = (sqrt(v') * rbc2) + eps
+ *   p' = p1 - (ss * (m' / d))
+ *   store p', m', v';  pout = narrow(p'), nearest even (float: p' itself)
+ * NaNs and infinities follow IEEE through these operations; nothing is
+ * skipped, nothing clamped.  A segment with counts[k] == 0 may have NULL
+ * pointers.  Stream-ordered, no host synchronization, no allocation.  The
+ * ranges of p, m, v, g and pout must not overlap each other (not checked).
+ * Mechanism: k_adamw_segs over the tile table of p as BINE_FLOAT (the
+ * sum-of-squares calls' rule: a workgroup per 32 KiB tile of p's 16-B aligned
+ * vectors, at least one per non-empty segment, a segment's first workgroup
+ * also taking the elements before the first and after the last vector), one
+ * launch per BINE_ADAMW_SEGS_PER_LAUNCH non-empty segments, descriptors by
+ * value; every workgroup forms gm itself.  With h = the elements before p's
+ * first 16-B boundary, a segment whose m + h and v + h are 16-B aligned, g + h
+ * aligned to 4 elements of gdtype and pout + h (if present) to 4 of odtype
+ * takes the vector body (4 consecutive elements per lane and access); any
+ * other segment takes the element body: the same operations through
+ * element-sized accesses, the same bits.
+ * BINE_ERR_ARG, before any HIP call, in this order: gdtype or odtype; n < 0 or
+ * n > BINE_MULTI_MAX; p, m, v, g or counts NULL with n > 0; then for p, m, v,
+ * g and (if given) pout in turn, a NULL buffer with a non-zero count or a
+ * buffer not aligned to its element size; gcoef not 8-byte aligned; grad_mul
+ * NaN, infinite or negative; the refusals of bine_adamw_consts. */
+#define BINE_ADAMW_SEGS_PER_LAUNCH 64
+int bine_adamw_consts(double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                      float out[8]);
+int bine_adamw_segments(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                        void *const *pout, const size_t *counts, int gdtype, int odtype, double lr, double beta1,
+                        double beta2, double eps, double weight_decay, int64_t step, const double *gcoef,
+                        double grad_mul, void *stream);
+/* Host only: the launches bine_adamw_segments issues for these addresses
+ * (pout NULL: none), element counts and types.  Returns the number of
+ * non-empty segments (may exceed cap) or -status (the list checks above); with
+ * `out`, one record of 5 uint64 per non-empty segment, in launch order:
+ * (launch, segment, its first workgroup in the launch, its workgroups, body: 0
+ * vector / 1 element). */
+int64_t bine_plan_adamw(int n, const uint64_t *p, const uint64_t *m, const uint64_t *v, const uint64_t *g,
+                        const uint64_t *pout, const size_t *counts, int gdtype, int odtype, uint64_t *out,
+                        int64_t cap);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -865,6 +934,25 @@ int bine_norm_multi(bine_comm_t comm, int algo, int n, const void *const *bufs, 
                     double *stats, void *stream);
 int bine_clip_multi(bine_comm_t comm, int algo, int n, void *const *bufs, const size_t *counts, int dtype,
                     double max_norm, double eps, double *stats, void *stream);
+/* ---- fused AdamW step and allgather of a bucket -------------------------------
+ * The last part of the sharded step: params[k] is the full parameter tensor,
+ * comm size * shard_counts[k] elements of odtype; p, m, v, g are this rank's
+ * shards (shard_counts[k] elements).  Bit for bit these two calls, both on the
+ * caller's stream:
+ *   bine_adamw_segments with pout[k] = params[k] + rank * shard_counts[k];
+ *   bine_allgather_multi(comm, ag_algo, n, NULL (in place), params,
+ *                        shard_counts, odtype, stream).
+ * k_adamw_segs is an ordinary launch, never captured; with graph mode on the
+ * inner allgather is captured and replayed as any call on those addresses.
+ * Refusals, before any exchange and any HIP call: those of bine_adamw_segments
+ * (params in pout's place), then those bine_allgather_multi makes without a
+ * communicator (a shard count above INT_MAX is BINE_ERR_ARG, an algorithm id
+ * outside the allgather range BINE_ERR_UNSUPPORTED), then comm == NULL is
+ * BINE_ERR_ARG. */
+int bine_adamw_multi(bine_comm_t comm, int ag_algo, int n, void *const *params, void *const *p, void *const *m,
+                     void *const *v, const void *const *g, const size_t *shard_counts, int gdtype, int odtype,
+                     double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                     const double *gcoef, double grad_mul, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -960,6 +1048,14 @@ int bine_loopback_run_norm_multi(bine_comm_t *comms, int nranks, int algo, int n
 int bine_loopback_run_clip_multi(bine_comm_t *comms, int nranks, int algo, int n, void *const *bufs,
                                  const size_t *counts, int dtype, double max_norm, double eps,
                                  double *const *stats, int *statuses);
+/* bine_adamw_multi on every virtual rank: params, p, m, v, g and shard_counts
+ * hold nranks * n entries, rank r's tensor k at [r * n + k]; gcoef one device
+ * pointer per rank, or NULL as a whole */
+int bine_loopback_run_adamw_multi(bine_comm_t *comms, int nranks, int ag_algo, int n, void *const *params,
+                                  void *const *p, void *const *m, void *const *v, const void *const *g,
+                                  const size_t *shard_counts, int gdtype, int odtype, double lr, double beta1,
+                                  double beta2, double eps, double weight_decay, int64_t step,
+                                  const double *const *gcoef, double grad_mul, int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

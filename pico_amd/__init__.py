@@ -42,6 +42,14 @@ then scales every tensor by min(1, max_norm / (norm + eps)) without a host
 read.  ``sumsq_segments`` and ``clip_segments`` are the local halves: a
 segmented sum of squares and a segmented scale whose factor is read from
 device memory.
+
+Optimizer step: ``adamw_segments`` is one fused AdamW update of a bucket of
+shards (float32 p, m, v in place; the gradient read once, scaled by a device
+coefficient; a 16-bit copy of the new parameter written where the allgather
+wants it), bit for bit a float32 statement of one operation per line;
+``adamw_multi`` adds the in-place ``allgather_multi`` of the full parameters.
+``adamw_consts`` and ``plan_adamw`` are the host views of its constants and
+launches.
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

@@ -60,6 +60,8 @@ UNIQUE_ID_BYTES = 128
 # per launch of k_copy_segs (BINE_COPY_SEGS_PER_LAUNCH)
 MULTI_MAX = 1024
 COPY_SEGS_PER_LAUNCH = 128
+# bine_adamw_segments: segments per launch of k_adamw_segs (BINE_ADAMW_SEGS_PER_LAUNCH)
+ADAMW_SEGS_PER_LAUNCH = 64
 
 
 class Prim(ctypes.Structure):
@@ -118,6 +120,7 @@ def lib():
         pass
     L = ctypes.CDLL(CORE)
     vp, sz, i, u32, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64
+    d = ctypes.c_double
     sigs = {
         "bine_status_string": ([i], ctypes.c_char_p),
         "bine_last_error": ([], ctypes.c_char_p),
@@ -188,6 +191,12 @@ def lib():
         "bine_clip_multi": ([vp, i, i, vp, vp, i, ctypes.c_double, ctypes.c_double, vp, vp], i),
         "bine_loopback_run_norm_multi": ([vp, i, i, i, vp, vp, i, vp, vp], i),
         "bine_loopback_run_clip_multi": ([vp, i, i, i, vp, vp, i, ctypes.c_double, ctypes.c_double, vp, vp], i),
+        "bine_adamw_consts": ([d, d, d, d, d, ctypes.c_int64, vp], i),
+        "bine_adamw_segments": ([i, vp, vp, vp, vp, vp, vp, i, i, d, d, d, d, d, ctypes.c_int64, vp, d, vp], i),
+        "bine_plan_adamw": ([i, vp, vp, vp, vp, vp, vp, i, i, vp, ctypes.c_int64], ctypes.c_int64),
+        "bine_adamw_multi": ([vp, i, i, vp, vp, vp, vp, vp, vp, i, i, d, d, d, d, d, ctypes.c_int64, vp, d, vp], i),
+        "bine_loopback_run_adamw_multi": ([vp, i, i, i, vp, vp, vp, vp, vp, vp, i, i, d, d, d, d, d, ctypes.c_int64,
+                                           vp, d, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

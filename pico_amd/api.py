@@ -790,6 +790,112 @@ def loopback_clip_multi(comms, algo, bufs, dtype, max_norm, eps, stats, counts=N
     return rc, list(st)
 
 
+# ---- fused AdamW step over a bucket of shards ----------------------------------------------
+
+def adamw_consts(lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int):
+    """The step's eight float32 constants (bine_adamw_consts, host only), each
+    computed in float64 and rounded once: dk = 1 - lr * weight_decay, b1,
+    1 - b1, b2, 1 - b2, rbc2 = 1 / sqrt(1 - b2^step), eps, ss = lr / (1 -
+    b1^step).  Returns a numpy float32 array of 8."""
+    import numpy as np
+    out = (ctypes.c_float * 8)()
+    check(lib().bine_adamw_consts(float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                                  out), "bine_adamw_consts")
+    return np.frombuffer(out, dtype=np.float32).copy()
+
+
+def _adamw_dtype(dtype, bufs, default: str = "float") -> int:
+    if isinstance(dtype, int):
+        return dtype
+    if dtype is None and not any(hasattr(b, "dtype") for b in (bufs or ())):
+        dtype = default
+    return _dtype(dtype, *(bufs or ()))
+
+
+def plan_adamw(p: Sequence[int], m: Sequence[int], v: Sequence[int], g: Sequence[int], pout, counts: Sequence[int],
+               gdtype, odtype="float"):
+    """The launches of adamw_segments for these device addresses (pout None:
+    no narrowed copy), element counts and types (bine_plan_adamw, host only):
+    a list of (launch, segment, first workgroup in the launch, workgroups,
+    body) per non-empty segment, body 0 = vector, 1 = element."""
+    n = len(counts)
+    if any(len(a) != n for a in (p, m, v, g)) or (pout is not None and len(pout) != n):
+        raise ValueError("plan_adamw: the address lists and counts differ in length")
+    arr = lambda a: (ctypes.c_uint64 * max(n, 1))(*a)  # noqa: E731
+    args = (n, arr(p), arr(m), arr(v), arr(g), None if pout is None else arr(pout),
+            (ctypes.c_size_t * max(n, 1))(*counts), _adamw_dtype(gdtype, ()), _adamw_dtype(odtype, ()))
+    cap = lib().bine_plan_adamw(*args, None, 0)
+    if cap < 0:
+        raise BineError(int(-cap), "bine_plan_adamw")
+    out = (ctypes.c_uint64 * (5 * max(cap, 1)))()
+    lib().bine_plan_adamw(*args, out, cap)
+    return [tuple(out[5 * t:5 * t + 5]) for t in range(cap)]
+
+
+def _adamw_lists(name: str, p, m, v, g, pout, counts):
+    n = len(p)
+    if any(len(a) != n for a in (m, v, g)) or (pout is not None and len(pout) != n):
+        raise ValueError(f"{name}: the tensor lists differ in length")
+    return _norm_counts(name, p, counts)
+
+
+def adamw_segments(p, m, v, g, pout=None, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
+                   eps: float = 1e-8, weight_decay: float = 0.01, step: int = 1, gcoef=None, grad_mul: float = 1.0,
+                   gdtype=None, odtype=None, counts=None, stream=None) -> None:
+    """One fused AdamW step of every shard (bine_adamw_segments): p, m, v float32
+    in place, g (float / float16 / bfloat16) read only, pout (optional, the same
+    three types) = the new parameter narrowed.  gcoef: a device float64 that
+    scales the gradient (clip_multi's stats[n + 1:]), None = 1.0; grad_mul a
+    host factor (1 / loss scale).  Per element, every line one float32
+    operation: gs = g * float32(gcoef * grad_mul); p1 = p * dk; m = m * b1 +
+    gs * (1 - b1); v = v * b2 + (gs * gs) * (1 - b2); d = sqrt(v) * rbc2 + eps;
+    p = p1 - ss * (m / d), constants as adamw_consts.  Empty shards may be
+    None; the tensors must not overlap."""
+    c = _adamw_lists("adamw_segments", p, m, v, g, pout, counts)
+    check(lib().bine_adamw_segments(len(p), _ptrs(p), _ptrs(m), _ptrs(v), _ptrs(g),
+                                    None if pout is None else _ptrs(pout), c, _adamw_dtype(gdtype, g),
+                                    _adamw_dtype(odtype, pout), float(lr), float(beta1), float(beta2), float(eps),
+                                    float(weight_decay), int(step), _ptr(gcoef), float(grad_mul),
+                                    _stream(stream, None)), "bine_adamw_segments")
+
+
+def adamw_multi(ag_algo, params, p, m, v, g, comm: Comm, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
+                eps: float = 1e-8, weight_decay: float = 0.01, step: int = 1, gcoef=None, grad_mul: float = 1.0,
+                gdtype=None, odtype=None, shard_counts=None, stream=None) -> None:
+    """bine_adamw_multi: adamw_segments with pout = this rank's slot of each full
+    parameter tensor params[k] (comm.size * shard_counts[k] elements of odtype),
+    then allgather_multi in place on params -- bit for bit those two calls."""
+    c = _adamw_lists("adamw_multi", p, m, v, g, params, shard_counts)
+    check(lib().bine_adamw_multi(comm.handle, _algo("allgather", ag_algo), len(p), _ptrs(params), _ptrs(p), _ptrs(m),
+                                 _ptrs(v), _ptrs(g), c, _adamw_dtype(gdtype, g), _adamw_dtype(odtype, params),
+                                 float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                                 _ptr(gcoef), float(grad_mul), _stream(stream, comm)), f"adamw_multi ({ag_algo})")
+
+
+def loopback_adamw_multi(comms, ag_algo, params, p, m, v, g, lr: float = 1e-3, beta1: float = 0.9,
+                         beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.01, step: int = 1,
+                         gcoef=None, grad_mul: float = 1.0, gdtype=None, odtype=None, shard_counts=None):
+    """adamw_multi on every virtual rank: params, p, m, v, g one list of tensors
+    per rank; shard_counts likewise (None: each p's numel()); gcoef one device
+    float64 per rank, or None.  Returns (status, per-rank statuses)."""
+    P = len(comms)
+    n = len(p[0])
+    if any(len(x) != P for x in (params, p, m, v, g)) or any(len(r) != n for x in (params, p, m, v, g) for r in x):
+        raise ValueError("loopback_adamw_multi: the ranks' lists differ in length")
+    if shard_counts is None:
+        shard_counts = [[t.numel() for t in r] for r in p]
+    flat = lambda x: [t for r in x for t in r]  # noqa: E731
+    fc = flat(shard_counts)
+    st = (ctypes.c_int * P)()
+    hs = (ctypes.c_void_p * P)(*[c.handle.value for c in comms])
+    rc = lib().bine_loopback_run_adamw_multi(
+        hs, P, _algo("allgather", ag_algo), n, _ptrs(flat(params)), _ptrs(flat(p)), _ptrs(flat(m)), _ptrs(flat(v)),
+        _ptrs(flat(g)), (ctypes.c_size_t * max(len(fc), 1))(*fc), _adamw_dtype(gdtype, flat(g)),
+        _adamw_dtype(odtype, flat(params)), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        int(step), None if gcoef is None else _ptrs(gcoef), float(grad_mul), st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -1182,6 +1288,7 @@ __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fus
            "loopback_reduce_scatter_multi", "loopback_allgather_multi",
            "sumsq_segments", "plan_sumsq", "clip_segments", "norm_multi", "clip_multi", "loopback_norm_multi",
            "loopback_clip_multi",
+           "adamw_consts", "plan_adamw", "adamw_segments", "adamw_multi", "loopback_adamw_multi",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

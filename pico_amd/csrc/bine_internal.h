@@ -284,6 +284,40 @@ int launch_clip_segments(int n, void *const *bufs, const size_t *counts, int dty
                          double max_norm, double eps, double *coef_out, void *stream);
 int launch_clip_segments_h16(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
                              double max_norm, double eps, double *coef_out, void *stream);
+// fused AdamW step over a list of shards (bine_adamw_segments, k_adamw_segs):
+// plan_norm_launches' table over p as BINE_FLOAT -- the same tiles, the same
+// first-workgroup rule -- cut into launches of at most kAdamwSegsPerLaunch
+// descriptors (five pointers and a count each: 128 would not fit the 4 KiB of
+// by-value arguments), tile0 rebased to each launch's first segment.
+constexpr int kAdamwSegsPerLaunch = BINE_ADAMW_SEGS_PER_LAUNCH;
+static_assert(kSegsPerLaunch % kAdamwSegsPerLaunch == 0 && kAdamwSegsPerLaunch <= 64,
+              "a SegLaunch splits into whole AdamW launches; AdamwLaunch::elem has one bit per slot");
+struct AdamwLaunch {
+  int nseg = 0;
+  int seg[kAdamwSegsPerLaunch];             // the caller's segment index per slot
+  uint32_t tile0[kAdamwSegsPerLaunch + 1];  // first workgroup per slot; [nseg] = the grid
+  uint64_t elem = 0;                        // bit s: slot s takes the element body
+};
+// the element size of the three types g and pout take (float, float16,
+// bfloat16), 0 otherwise
+size_t adamw_esz(int dtype);
+// The checks of the five lists that need no device, in the header's order, then
+// the launches.  pout NULL: no 16-bit copy.  BINE_SUCCESS or BINE_ERR_ARG.
+int plan_adamw_launches(int n, const uint64_t *p, const uint64_t *m, const uint64_t *v, const uint64_t *g,
+                        const uint64_t *pout, const size_t *counts, int gdtype, int odtype,
+                        std::vector<AdamwLaunch> &out);
+// every check of bine_adamw_segments, nothing launched (bine_adamw_multi runs
+// it before it looks at its communicator)
+int adamw_args(int n, void *const *p, void *const *m, void *const *v, const void *const *g, void *const *pout,
+               const size_t *counts, int gdtype, int odtype, double lr, double beta1, double beta2, double eps,
+               double weight_decay, int64_t step, const double *gcoef, double grad_mul, float consts[8],
+               std::vector<AdamwLaunch> *ls);
+// bine_adamw_segments: adamw_args, then k_adamw_segs per launch (kernels_h16.o:
+// the compilation that holds the 16-bit conversions)
+int launch_adamw_segments_h16(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                              void *const *pout, const size_t *counts, int gdtype, int odtype, double lr,
+                              double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                              const double *gcoef, double grad_mul, void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -2059,6 +2059,14 @@ int bine_clip_segments(int n, void *const *bufs, const size_t *counts, int dtype
   return launch_clip_segments(n, bufs, counts, dtype, norm2, max_norm, eps, coef_out, stream);  // likewise
 }
 
+int bine_adamw_segments(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                        void *const *pout, const size_t *counts, int gdtype, int odtype, double lr, double beta1,
+                        double beta2, double eps, double weight_decay, int64_t step, const double *gcoef,
+                        double grad_mul, void *stream) {
+  return launch_adamw_segments_h16(n, p, m, v, g, pout, counts, gdtype, odtype, lr, beta1, beta2, eps, weight_decay,
+                                   step, gcoef, grad_mul, stream);  // checks its arguments
+}
+
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream) {
   return launch_fill_pico(buf, count, dtype, seed, stream);
 }
@@ -2691,6 +2699,39 @@ int bine_clip_multi(bine_comm_t c, int algo, int n, void *const *bufs, const siz
   return launch_clip_segments(n, bufs, counts, dtype, stats + n, max_norm, eps, stats + n + 1, stream);
 }
 
+// ---- fused AdamW step and allgather of a bucket (bine_amd.h) -----------------------------
+
+// the checks that need no communicator: bine_adamw_segments' with params in
+// pout's place (a shard's offset keeps its tensor's element alignment), then
+// the in-place allgather's
+static int adamw_multi_args(int ag_algo, int n, void *const *params, void *const *p, void *const *m, void *const *v,
+                            const void *const *g, const size_t *shard_counts, int gdtype, int odtype, double lr,
+                            double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                            const double *gcoef, double grad_mul) {
+  if (const int rc = adamw_args(n, p, m, v, g, params, shard_counts, gdtype, odtype, lr, beta1, beta2, eps,
+                                weight_decay, step, gcoef, grad_mul, nullptr, nullptr))
+    return rc;
+  return shard_args(false, ag_algo, n, nullptr, params, shard_counts, odtype, 0, 1.0, 0);
+}
+
+int bine_adamw_multi(bine_comm_t c, int ag_algo, int n, void *const *params, void *const *p, void *const *m,
+                     void *const *v, const void *const *g, const size_t *shard_counts, int gdtype, int odtype,
+                     double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                     const double *gcoef, double grad_mul, void *stream) {
+  if (const int rc = adamw_multi_args(ag_algo, n, params, p, m, v, g, shard_counts, gdtype, odtype, lr, beta1, beta2,
+                                      eps, weight_decay, step, gcoef, grad_mul))
+    return rc;
+  if (!c) return BINE_ERR_ARG;
+  const size_t osz = adamw_esz(odtype);
+  std::vector<void *> pout((size_t)n);
+  for (int k = 0; k < n; k++)
+    pout[k] = shard_counts[k] ? (char *)params[k] + (size_t)c->rank * shard_counts[k] * osz : nullptr;
+  if (const int rc = launch_adamw_segments_h16(n, p, m, v, g, pout.data(), shard_counts, gdtype, odtype, lr, beta1,
+                                               beta2, eps, weight_decay, step, gcoef, grad_mul, stream))
+    return rc;
+  return bine_allgather_multi(c, ag_algo, n, nullptr, params, shard_counts, odtype, stream);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -2996,6 +3037,31 @@ int bine_loopback_run_clip_multi(bine_comm_t *comms, int nranks, int algo, int n
                                  const size_t *counts, int dtype, double max_norm, double eps, double *const *stats,
                                  int *statuses) {
   return loopback_norm(true, comms, nranks, algo, n, bufs, counts, dtype, max_norm, eps, stats, statuses);
+}
+
+int bine_loopback_run_adamw_multi(bine_comm_t *comms, int nranks, int ag_algo, int n, void *const *params,
+                                  void *const *p, void *const *m, void *const *v, const void *const *g,
+                                  const size_t *shard_counts, int gdtype, int odtype, double lr, double beta1,
+                                  double beta2, double eps, double weight_decay, int64_t step,
+                                  const double *const *gcoef, double grad_mul, int *statuses) {
+  // rank r's part of a list of nranks * n entries
+  auto at = [&](auto *list, int r) { return list && n > 0 ? list + (size_t)r * n : list; };
+  // before any thread, stream or HIP call: what a rank would refuse without a communicator
+  int bad = BINE_SUCCESS;
+  for (int r = 0; !bad && r < nranks; r++)
+    bad = adamw_multi_args(ag_algo, n, at(params, r), at(p, r), at(m, r), at(v, r), at(g, r), at(shard_counts, r),
+                           gdtype, odtype, lr, beta1, beta2, eps, weight_decay, step, gcoef ? gcoef[r] : nullptr,
+                           grad_mul);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return bad;
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_adamw_multi(comms[r], ag_algo, n, at(params, r), at(p, r), at(m, r), at(v, r), at(g, r),
+                            at(shard_counts, r), gdtype, odtype, lr, beta1, beta2, eps, weight_decay, step,
+                            gcoef ? gcoef[r] : nullptr, grad_mul, comms[r]->stream);
+  });
 }
 
 int bine_loopback_run_reduce_scatter_wide(bine_comm_t *comms, int n, int algo, const void *const *sbufs,

@@ -2023,6 +2023,216 @@ int launch_narrow_h16(const void *in32, void *out16, size_t count, int dtype, vo
     return status(hipGetLastError());
   });
 }
+
+// ----------------------------------------------------------------------------
+// k_adamw_segs: one AdamW step over a list of shards (bine_adamw_segments,
+// bine_amd.h).  p, m, v are binary32 and updated in place, g (G: float,
+// float16, bfloat16) is read only, pout (O, optional) receives the new
+// parameter narrowed.  k_scale_segs' dispatch -- descriptors by value, the grid
+// the concatenation of the segments' tiles, seg_of_tile's search -- over
+// plan_norm_launches' table of p, cut at kAdamwSegsPerLaunch descriptors
+// (plan_adamw_launches): a tile is kBlock * kScaleU 16-B aligned vectors of p,
+// and a segment's first workgroup also takes the elements before the first
+// and after the last vector.
+//
+// Every line of adamw1 is one correctly rounded binary32 operation
+// (-ffp-contract=off: no FMA; IEEE division and square root; subnormals kept).
+// The widened gradient and the new parameter pass through widen1 / narrow1,
+// whose empty asm keeps a conversion from folding into a v_fma_mix*.
+//
+// A segment whose m, v, g and pout stand on a 4-element boundary wherever p
+// stands on a 16-B one takes the vector body (a lane handles 4 consecutive
+// elements: 16-B accesses of p, m, v, 8-B or 16-B ones of g and pout; all
+// loads of a full tile issued before the first use, non-temporal stores); any
+// other segment takes the element body (AdamwSegs::elem, set by the host), the
+// same arithmetic through element-sized accesses.
+struct AdamwSeg {
+  float *p, *m, *v;
+  const void *g;
+  void *pout;  // NULL when the call has none
+  uint64_t n;  // elements
+};
+struct AdamwSegs {
+  uint32_t nseg;
+  uint32_t tile0[kAdamwSegsPerLaunch + 1];
+  uint64_t elem;        // bit s: slot s takes the element body
+  const double *gcoef;  // NULL: 1.0
+  double grad_mul;
+  float c[8];  // bine_adamw_consts: dk, b1, 1 - b1, b2, 1 - b2, rbc2, eps, ss
+  AdamwSeg s[kAdamwSegsPerLaunch];
+};
+static_assert(sizeof(AdamwSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// 4 consecutive elements of T as one access
+template <typename T>
+using vec4_of = std::conditional_t<sizeof(T) == 4, u32x4, u32x2>;
+
+template <typename G>
+__device__ __forceinline__ float adamw_widen(G x) {
+  if constexpr (std::is_same_v<G, float>) return x;
+  else return widen1<G>(x);
+}
+template <typename O>
+__device__ __forceinline__ O adamw_narrow(float f) {
+  if constexpr (std::is_same_v<O, float>) return f;
+  else return narrow1<O>(f);
+}
+
+__device__ __forceinline__ void adamw1(float &p, float &m, float &v, float g, float gm, const float (&c)[8]) {
+  const float gs = g * gm;
+  const float p1 = p * c[0];
+  m = (m * c[1]) + (gs * c[2]);
+  v = (v * c[3]) + ((gs * gs) * c[4]);
+  const float d = (__builtin_sqrtf(v) * c[5]) + c[6];
+  p = p1 - (c[7] * (m / d));
+}
+
+// one lane's 4 elements: vector i of the segment's body
+template <typename G, typename O, bool PO, bool NT>
+__device__ __forceinline__ void adamw_vec(u32x4 xp, u32x4 xm, u32x4 xv, vec4_of<G> xg, float gm, const float (&c)[8],
+                                          u32x4 *vp, u32x4 *vm, u32x4 *vv, [[maybe_unused]] vec4_of<O> *vo, size_t i) {
+  float p[4], m[4], v[4];
+  G g[4];
+  [[maybe_unused]] O o[4];
+  __builtin_memcpy(p, &xp, 16);
+  __builtin_memcpy(m, &xm, 16);
+  __builtin_memcpy(v, &xv, 16);
+  __builtin_memcpy(g, &xg, sizeof g);
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    adamw1(p[e], m[e], v[e], adamw_widen<G>(g[e]), gm, c);
+    if constexpr (PO) o[e] = adamw_narrow<O>(p[e]);
+  }
+  __builtin_memcpy(&xp, p, 16);
+  __builtin_memcpy(&xm, m, 16);
+  __builtin_memcpy(&xv, v, 16);
+  if constexpr (NT) {
+    __builtin_nontemporal_store(xp, vp + i);
+    __builtin_nontemporal_store(xm, vm + i);
+    __builtin_nontemporal_store(xv, vv + i);
+  } else {
+    vp[i] = xp;
+    vm[i] = xm;
+    vv[i] = xv;
+  }
+  if constexpr (PO) {
+    vec4_of<O> xo;
+    __builtin_memcpy(&xo, o, sizeof o);
+    if constexpr (NT) __builtin_nontemporal_store(xo, vo + i);
+    else vo[i] = xo;
+  }
+}
+
+template <typename G, typename O, bool PO>
+__global__ __launch_bounds__(kBlock) void k_adamw_segs(AdamwSegs a) {
+  using GV = vec4_of<G>;
+  using OV = vec4_of<O>;
+  const uint32_t t = blockIdx.x, k = seg_of_tile(a.tile0, a.nseg, t), wt = t - a.tile0[k];
+  float *p = a.s[k].p, *m = a.s[k].m, *v = a.s[k].v;
+  const G *g = static_cast<const G *>(a.s[k].g);
+  [[maybe_unused]] O *po = static_cast<O *>(a.s[k].pout);
+  const size_t n = a.s[k].n;
+  const size_t h = ((16 - ((uintptr_t)p & 15)) & 15) / 4, he = h < n ? h : n, nvec = (n - he) / 4;
+  const bool elem = (a.elem >> k) & 1;
+  u32x4 *vp = reinterpret_cast<u32x4 *>(p + he), *vm = reinterpret_cast<u32x4 *>(m + he);
+  u32x4 *vv = reinterpret_cast<u32x4 *>(v + he);
+  const GV *vg = reinterpret_cast<const GV *>(g + he);
+  OV *vo = nullptr;
+  if constexpr (PO) vo = reinterpret_cast<OV *>(po + he);
+  const size_t base = (size_t)wt * kBlock * kScaleU + threadIdx.x;
+  const bool full = !elem && ((size_t)wt + 1) * kBlock * kScaleU <= nvec;  // workgroup-uniform
+  u32x4 xp[kScaleU], xm[kScaleU], xv[kScaleU];
+  GV xg[kScaleU];
+  if (full) {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      xp[u] = vp[i];
+      xm[u] = vm[i];
+      xv[u] = vv[i];
+      xg[u] = vg[i];
+    }
+  }
+  // gm = (float)(c * grad_mul): the product in binary64, one rounding
+  const double cf = a.gcoef ? *a.gcoef : 1.0;
+  const float gm = (float)(cf * a.grad_mul);
+  auto one = [&](size_t i) {
+    float pp = p[i], mm = m[i], vx = v[i];
+    adamw1(pp, mm, vx, adamw_widen<G>(g[i]), gm, a.c);
+    p[i] = pp;
+    m[i] = mm;
+    v[i] = vx;
+    if constexpr (PO) po[i] = adamw_narrow<O>(pp);
+  };
+  if (wt == 0) {  // head and tail elements of this segment
+    for (size_t i = threadIdx.x; i < he; i += kBlock) one(i);
+    for (size_t i = he + nvec * 4 + threadIdx.x; i < n; i += kBlock) one(i);
+  }
+  if (full) {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++)
+      adamw_vec<G, O, PO, true>(xp[u], xm[u], xv[u], xg[u], gm, a.c, vp, vm, vv, vo, base + (size_t)u * kBlock);
+  } else if (!elem) {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if (i < nvec) adamw_vec<G, O, PO, false>(vp[i], vm[i], vv[i], vg[i], gm, a.c, vp, vm, vv, vo, i);
+    }
+  } else {  // the tile's elements one by one
+    const size_t lo = he + (size_t)wt * kBlock * kScaleU * 4, end = he + nvec * 4;
+    const size_t hi = lo + (size_t)kBlock * kScaleU * 4 < end ? lo + (size_t)kBlock * kScaleU * 4 : end;
+    for (size_t i = lo + threadIdx.x; i < hi; i += kBlock) one(i);
+  }
+}
+
+// f(dtype_tag<T, dtype>{}) for the three types g and pout take
+template <typename F>
+static int with_adamw_dtype(int dtype, F &&f) {
+  switch (dtype) {
+    case BINE_FLOAT: return f(dtype_tag<float, BINE_FLOAT>{});
+    case BINE_FLOAT16: return f(dtype_tag<F16, BINE_FLOAT16>{});
+    case BINE_BFLOAT16: return f(dtype_tag<BF16, BINE_BFLOAT16>{});
+    default: return BINE_ERR_ARG;
+  }
+}
+
+int launch_adamw_segments_h16(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                              void *const *pout, const size_t *counts, int gdtype, int odtype, double lr,
+                              double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                              const double *gcoef, double grad_mul, void *stream) {
+  AdamwSegs a;
+  std::vector<AdamwLaunch> ls;
+  if (const int rc = adamw_args(n, p, m, v, g, pout, counts, gdtype, odtype, lr, beta1, beta2, eps, weight_decay,
+                                step, gcoef, grad_mul, a.c, &ls))
+    return rc;
+  a.gcoef = gcoef;
+  a.grad_mul = grad_mul;
+  hipStream_t st = (hipStream_t)stream;
+  return with_adamw_dtype(gdtype, [&](auto gtag) {
+    using G = typename decltype(gtag)::type;
+    return with_adamw_dtype(odtype, [&](auto otag) -> int {
+      using O = typename decltype(otag)::type;
+      for (const AdamwLaunch &L : ls) {
+        a.nseg = (uint32_t)L.nseg;
+        a.elem = L.elem;
+        for (int s = 0; s < L.nseg; s++) {
+          const int k = L.seg[s];
+          a.tile0[s] = L.tile0[s];
+          a.s[s] = {(float *)p[k], (float *)m[k], (float *)v[k], g[k], pout ? pout[k] : nullptr, (uint64_t)counts[k]};
+        }
+        for (int s = L.nseg; s <= kAdamwSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nseg];
+        for (int s = L.nseg; s < kAdamwSegsPerLaunch; s++) a.s[s] = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+        const dim3 grid(L.tile0[L.nseg]), blk(kBlock);
+        // without pout one instantiation per G serves every odtype
+        if (pout) hipLaunchKernelGGL((k_adamw_segs<G, O, true>), grid, blk, 0, st, a);
+        else hipLaunchKernelGGL((k_adamw_segs<G, float, false>), grid, blk, 0, st, a);
+        if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+      }
+      return BINE_SUCCESS;
+    });
+  });
+}
 #endif  // BINE_OPSET == 2
 
 #if BINE_OPSET == 0

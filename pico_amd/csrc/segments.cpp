@@ -11,8 +11,12 @@
 // launch_copy_shards issues as k_copy_shards (tools/shards_check.cpp).  The
 // segmented sum of squares and the segmented scale walk plan_seg_launches'
 // table over the buffers themselves: plan_norm_launches / bine_plan_sumsq
-// (tools/sumsq_check.cpp).
+// (tools/sumsq_check.cpp).  The fused AdamW step walks plan_norm_launches' table
+// over p and cuts it at kAdamwSegsPerLaunch descriptors: plan_adamw_launches /
+// bine_plan_adamw, with the step's constants (bine_adamw_consts) beside them
+// (tools/adamw_check.cpp).
 #include <algorithm>
+#include <cmath>
 
 #include "bine_internal.h"
 
@@ -133,7 +137,109 @@ int plan_norm_launches(int n, const uint64_t *addrs, const size_t *counts, int d
   return BINE_SUCCESS;
 }
 
+size_t adamw_esz(int dtype) { return dtype == BINE_DOUBLE ? 0 : norm_esz(dtype); }
+
+// one of m / v / g / pout against the list rule p has passed: a NULL buffer
+// with a non-zero count, a buffer not aligned to its element
+static int adamw_list(int n, const uint64_t *a, const size_t *counts, size_t esz) {
+  for (int k = 0; k < n; k++)
+    if (counts[k] && (!a[k] || a[k] % esz)) return BINE_ERR_ARG;
+  return BINE_SUCCESS;
+}
+
+int plan_adamw_launches(int n, const uint64_t *p, const uint64_t *m, const uint64_t *v, const uint64_t *g,
+                        const uint64_t *pout, const size_t *counts, int gdtype, int odtype,
+                        std::vector<AdamwLaunch> &out) {
+  out.clear();
+  const size_t gsz = adamw_esz(gdtype), osz = adamw_esz(odtype);
+  if (!gsz || !osz) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX) return BINE_ERR_ARG;
+  if (n > 0 && (!p || !m || !v || !g || !counts)) return BINE_ERR_ARG;
+  std::vector<SegLaunch> ls;
+  if (const int rc = plan_norm_launches(n, p, counts, BINE_FLOAT, ls, nullptr)) return rc;
+  if (adamw_list(n, m, counts, 4) || adamw_list(n, v, counts, 4) || adamw_list(n, g, counts, gsz)) return BINE_ERR_ARG;
+  if (pout && adamw_list(n, pout, counts, osz)) return BINE_ERR_ARG;
+  for (const SegLaunch &L : ls)
+    for (int s0 = 0; s0 < L.nseg; s0 += kAdamwSegsPerLaunch) {
+      out.emplace_back();
+      AdamwLaunch &A = out.back();
+      A.nseg = std::min(kAdamwSegsPerLaunch, L.nseg - s0);
+      for (int s = 0; s < A.nseg; s++) {
+        const int k = L.seg[s0 + s];
+        A.seg[s] = k;
+        A.tile0[s] = L.tile0[s0 + s] - L.tile0[s0];
+        // h: the elements before p's first 16-B boundary; the vector body needs
+        // every other operand on a boundary of its own 4-element vector there
+        const uint64_t h = ((16 - (p[k] & 15)) & 15) / 4;
+        const bool vec = (m[k] + 4 * h) % 16 == 0 && (v[k] + 4 * h) % 16 == 0 && (g[k] + gsz * h) % (4 * gsz) == 0 &&
+                         (!pout || (pout[k] + osz * h) % (4 * osz) == 0);
+        if (!vec) A.elem |= (uint64_t)1 << s;
+      }
+      A.tile0[A.nseg] = L.tile0[s0 + A.nseg] - L.tile0[s0];
+    }
+  return BINE_SUCCESS;
+}
+
+int adamw_args(int n, void *const *p, void *const *m, void *const *v, const void *const *g, void *const *pout,
+               const size_t *counts, int gdtype, int odtype, double lr, double beta1, double beta2, double eps,
+               double weight_decay, int64_t step, const double *gcoef, double grad_mul, float consts[8],
+               std::vector<AdamwLaunch> *ls) {
+  if (!adamw_esz(gdtype) || !adamw_esz(odtype)) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!p || !m || !v || !g || !counts))) return BINE_ERR_ARG;
+  std::vector<uint64_t> a((size_t)5 * (n > 0 ? n : 1));
+  uint64_t *pa = a.data(), *ma = pa + n, *va = ma + n, *ga = va + n, *oa = ga + n;
+  for (int k = 0; k < n; k++) {
+    pa[k] = (uint64_t)(uintptr_t)p[k], ma[k] = (uint64_t)(uintptr_t)m[k], va[k] = (uint64_t)(uintptr_t)v[k];
+    ga[k] = (uint64_t)(uintptr_t)g[k], oa[k] = pout ? (uint64_t)(uintptr_t)pout[k] : 0;
+  }
+  std::vector<AdamwLaunch> local;
+  if (const int rc = plan_adamw_launches(n, pa, ma, va, ga, pout ? oa : nullptr, counts, gdtype, odtype,
+                                         ls ? *ls : local))
+    return rc;
+  if ((uintptr_t)gcoef & 7) return BINE_ERR_ARG;
+  if (!(grad_mul >= 0.0) || std::isinf(grad_mul)) return BINE_ERR_ARG;  // NaN, negative or infinite
+  float c[8];
+  return bine_adamw_consts(lr, beta1, beta2, eps, weight_decay, step, consts ? consts : c);
+}
+
 }  // namespace bine
+
+extern "C" int bine_adamw_consts(double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                                 float out[8]) {
+  // negative or NaN; a beta outside [0, 1) or NaN
+  if (!(lr >= 0.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return BINE_ERR_ARG;
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return BINE_ERR_ARG;
+  if (step < 1 || !out) return BINE_ERR_ARG;
+  // binary64 throughout, one rounding (nearest even) to binary32 each
+  out[0] = (float)(1.0 - lr * weight_decay);
+  out[1] = (float)beta1;
+  out[2] = (float)(1.0 - beta1);
+  out[3] = (float)beta2;
+  out[4] = (float)(1.0 - beta2);
+  out[5] = (float)(1.0 / std::sqrt(1.0 - std::pow(beta2, (double)step)));
+  out[6] = (float)eps;
+  out[7] = (float)(lr / (1.0 - std::pow(beta1, (double)step)));
+  return BINE_SUCCESS;
+}
+
+extern "C" int64_t bine_plan_adamw(int n, const uint64_t *p, const uint64_t *m, const uint64_t *v, const uint64_t *g,
+                                   const uint64_t *pout, const size_t *counts, int gdtype, int odtype, uint64_t *out,
+                                   int64_t cap) {
+  std::vector<bine::AdamwLaunch> ls;
+  const int rc = bine::plan_adamw_launches(n, p, m, v, g, pout, counts, gdtype, odtype, ls);
+  if (rc) return -(int64_t)rc;
+  int64_t nt = 0;
+  for (size_t l = 0; l < ls.size(); l++) {
+    const bine::AdamwLaunch &A = ls[l];
+    for (int s = 0; s < A.nseg; s++, nt++)
+      if (out && nt < cap) {
+        uint64_t *e = out + 5 * nt;
+        e[0] = l, e[1] = (uint64_t)A.seg[s], e[2] = A.tile0[s], e[3] = A.tile0[s + 1] - A.tile0[s];
+        e[4] = (A.elem >> s) & 1;
+      }
+  }
+  return nt;
+}
 
 extern "C" int64_t bine_plan_sumsq(int n, const uint64_t *addrs, const size_t *counts, int dtype) {
   std::vector<bine::SegLaunch> ls;

@@ -1,0 +1,32 @@
+"""The fused AdamW step and allgather over the RCCL and direct transports in real
+processes, graph mode included (tools/adamw_check.py)."""
+import os
+import sys
+
+import pytest
+
+import _sub
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# three times the measured wall time of the tool, floored at 60 s (profiles/adamw_check.txt)
+TIMEOUT = {2: 60}
+
+
+@pytest.mark.timeout(200)
+@pytest.mark.parametrize("P", [2])
+def test_adamw_processes(P):
+    """P processes on the one GPU, the shards of seven tensors each: adamw_multi
+    (float and bfloat16, ring) over RCCL P2P (literal and flat) and over the
+    direct transport, then in graph mode; every rank's p', m', v' vs the numpy
+    float32 statement and its params vs the concatenation of all ranks'
+    narrowed p'"""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    # 4 HW queues per rank, HIP's default: with fewer, graph mode keeps a call that
+    # makes RCCL calls eager and the tool's replay case would have nothing to replay
+    r = _sub.run_kw([sys.executable, "-u", os.path.join(ROOT, "tools", "adamw_check.py"), str(P)], env=env,
+                    capture_output=True, text=True, timeout=TIMEOUT[P], ranks=P, queues=4)
+    lines = [x for x in r.stdout.splitlines() if "MISMATCH" in x or "RESULT" in x or " ok, " in x]
+    assert r.returncode == 0, "\n".join(lines[:40]) + "\n" + r.stderr[-2000:]
+    assert f"RESULT P={P}" in r.stdout
