@@ -419,8 +419,9 @@ int64_t bine_plan_sumsq(int n, const uint64_t *addrs, const size_t *counts, int 
 int bine_clip_segments(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
                        double max_norm, double eps, double *coef_out, void *stream);
 /* ---- fused AdamW step over a list of shards -----------------------------------
- * What a sharded training step does between bine_clip_multi and
- * bine_allgather_multi (bine_adamw_multi below): one decoupled-weight-decay
+ * What a sharded training step does between the global norm (bine_norm_multi
+ * and the coefficient, see gcoef) and bine_allgather_multi (bine_adamw_multi
+ * below): one decoupled-weight-decay
  * Adam update of every shard in one pass -- the gradient read once and never
  * rewritten, the clip coefficient read from device memory, the 16-bit copy of
  * the new parameter stored where the allgather wants it.
@@ -439,7 +440,11 @@ int bine_clip_segments(int n, void *const *bufs, const size_t *counts, int dtype
  * and is read only; pout may be NULL as a whole, otherwise it has odtype and is
  * written only (gdtype, odtype: BINE_FLOAT, BINE_FLOAT16 or BINE_BFLOAT16;
  * odtype is checked even without pout).  gcoef: a device pointer to one
- * double, NULL meaning 1.0 (intended: bine_clip_multi's &stats[n + 1]);
+ * double, NULL meaning 1.0 (intended: the clip coefficient of a gradient that
+ * has NOT been scaled -- bine_norm_multi, then bine_clip_segments with n = 0,
+ * norm2 = &stats[n], coef_out = &stats[n + 1], which stores c and touches no
+ * tensor.  bine_clip_multi scales g in place: after it pass NULL, or c is
+ * applied twice);
  * grad_mul: a host double, 1 / loss scale say.  Per element, every line one
  * correctly rounded binary32 operation, nothing contracted, subnormals kept:
  *   gm = (float)(c * grad_mul)          c = gcoef ? *gcoef : 1.0; the product in
@@ -923,7 +928,9 @@ int bine_allgather_multi(bine_comm_t comm, int algo, int n, const void *const *s
  * call on that address.
  * bine_clip_multi: stats has n + 2 doubles; bine_norm_multi into stats[0..n],
  * then bine_clip_segments with norm2 = &stats[n], coef_out = &stats[n + 1]:
- * every rank scales by the same coefficient bits.
+ * every rank scales by the same coefficient bits.  The shards ARE scaled: a
+ * caller that hands the coefficient on (bine_adamw_segments' gcoef) instead
+ * wants bine_norm_multi followed by bine_clip_segments with n = 0.
  * Refusals, before any exchange and any HIP call, in this order: BINE_ERR_ARG
  * for the dtype; the list checks of bine_sumsq_segments; stats NULL or not
  * 8-byte aligned; (clip) max_norm or eps negative or NaN; then an algorithm id

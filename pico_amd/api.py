@@ -740,13 +740,32 @@ def norm_multi(algo, bufs, dtype, comm: Comm, counts=None, stats=None, stream=No
     return stats
 
 
+def _coef_only_args(name: str, max_norm, eps) -> None:
+    """scale=False has no C call of its own to refuse these before the exchange"""
+    if not float(max_norm) >= 0.0 or not float(eps) >= 0.0:
+        raise BineError(1, f"{name}: max_norm or eps negative or NaN")
+
+
 def clip_multi(algo, bufs, dtype, comm: Comm, max_norm: float, eps: float = 0.0, counts=None, stats=None,
-               stream=None):
+               stream=None, scale: bool = True):
     """bine_clip_multi: norm_multi into stats[0..n], then every tensor scaled in
     place by c = min(1, max_norm / (sqrt(stats[n]) + eps)) (clip_segments);
     stats[n + 1] = c, the same bits on every rank.  stats: n + 2 float64.
+    scale=False: the same statistics and coefficient, no tensor touched --
+    norm_multi, then clip_segments on an empty list with norm2 = &stats[n],
+    coef_out = &stats[n + 1].  That is the form to put in front of adamw_multi
+    (gcoef=stats[n + 1:]), which applies the coefficient itself: after
+    scale=True the gradient is clipped already and gcoef must stay None, or the
+    coefficient is applied twice.  (max_norm and eps are refused first then.)
     Returns stats."""
     stats = _stats(bufs, stats, 2)
+    if not scale:
+        _coef_only_args("clip_multi", max_norm, eps)
+        norm_multi(algo, bufs, dtype, comm, counts=counts, stats=stats, stream=stream)
+        a = _ptr(stats)
+        clip_segments([], a + 8 * len(bufs), max_norm, eps, dtype=_norm_dtype(dtype, bufs), counts=[],
+                      coef_out=a + 8 * (len(bufs) + 1), stream=_stream(stream, comm))
+        return stats
     c = _norm_counts("clip_multi", bufs, counts)
     check(lib().bine_clip_multi(comm.handle, _algo("allreduce", algo), len(bufs), _ptrs(bufs), c,
                                 _norm_dtype(dtype, bufs), float(max_norm), float(eps), _ptr(stats),
@@ -779,9 +798,20 @@ def loopback_norm_multi(comms, algo, bufs, dtype, stats, counts=None):
     return rc, list(st)
 
 
-def loopback_clip_multi(comms, algo, bufs, dtype, max_norm, eps, stats, counts=None):
+def loopback_clip_multi(comms, algo, bufs, dtype, max_norm, eps, stats, counts=None, scale=True):
     """as loopback_norm_multi, clip_multi on every virtual rank; stats: n + 2
-    float64 per rank."""
+    float64 per rank.  scale=False as clip_multi's: the coefficient alone, each
+    rank's clip_segments on its communicator's stream."""
+    if not scale:
+        _coef_only_args("loopback_clip_multi", max_norm, eps)
+        rc, st = loopback_norm_multi(comms, algo, bufs, dtype, stats, counts=counts)
+        if rc == 0 and not any(st):
+            n, dt = len(bufs[0]), _norm_dtype(dtype, [b for r in bufs for b in r])
+            for cm, s in zip(comms, stats):
+                a = _ptr(s)
+                clip_segments([], a + 8 * n, max_norm, eps, dtype=dt, counts=[], coef_out=a + 8 * (n + 1),
+                              stream=cm.stream)
+        return rc, st
     st = (ctypes.c_int * len(comms))()
     hs = (ctypes.c_void_p * len(comms))(*[c.handle.value for c in comms])
     n, flat, c = _loopback_norm("loopback_clip_multi", bufs, stats, counts)
@@ -845,7 +875,8 @@ def adamw_segments(p, m, v, g, pout=None, lr: float = 1e-3, beta1: float = 0.9, 
     """One fused AdamW step of every shard (bine_adamw_segments): p, m, v float32
     in place, g (float / float16 / bfloat16) read only, pout (optional, the same
     three types) = the new parameter narrowed.  gcoef: a device float64 that
-    scales the gradient (clip_multi's stats[n + 1:]), None = 1.0; grad_mul a
+    scales the gradient (clip_multi(..., scale=False)'s stats[n + 1:] -- after a
+    clip that scaled g in place pass None), None = 1.0; grad_mul a
     host factor (1 / loss scale).  Per element, every line one float32
     operation: gs = g * float32(gcoef * grad_mul); p1 = p * dk; m = m * b1 +
     gs * (1 - b1); v = v * b2 + (gs * gs) * (1 - b2); d = sqrt(v) * rbc2 + eps;

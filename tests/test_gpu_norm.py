@@ -300,6 +300,58 @@ def test_clip_segments(dev, dtype):
     assert coef.read().view(np.float64)[0] == 0.25
 
 
+def round_once(y, dtype):
+    """float64 -> the 16-bit type's bits, one rounding to nearest even (normal range)"""
+    if dtype == "float16":
+        return np.asarray(y, dtype=np.float64).astype(np.float16).view(np.uint16)
+    m, e = np.frexp(np.asarray(y, dtype=np.float64))
+    r = np.ldexp(np.round(m * 256.0), e - 8)          # 8 significant bits; numpy rounds halves to even
+    assert (np.abs(r[r != 0]) > 1e-30).all()
+    return H.from_f32(r.astype(np.float32), dtype)    # exact: r is a bfloat16 value
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+def test_clip_segments_against_the_host(dev, dtype):
+    """the clipped tensors against the product computed here, no kernel of the
+    library involved: float and double bit for bit (x * (float)c, x * c); the
+    16-bit types bit for bit the header's two roundings (binary32 product, then
+    the type), hence the single rounding of the float64 product x * c wherever
+    the two agree, and never more than one unit in the last place from it"""
+    import optim_ref as R
+    eps = 1e-6
+    c = R.clip_coef(100.0, MAXN, eps)
+    assert 0.29 < c < 0.3
+    b = bucket(dtype, mixed_specs(dtype, 12), 13, "normal")
+    nd, coef = dev_doubles([100.0]), Guarded(1)
+    pico_amd.clip_segments(b.ptrs(), nd, MAXN, eps, dtype=dtype, counts=b.counts, coef_out=coef.ptr())
+    torch.cuda.synchronize()
+    assert coef.read().view(np.float64)[0] == c
+    parts, guards = b.read()
+    assert guards, "bytes around a tensor changed"
+    cf = np.float64(np.float32(c))
+    agree = total = 0
+    for k, cnt in enumerate(b.counts):
+        x = b.values(k)                                  # the stored values, exactly, as float64
+        if dtype == "double":
+            assert parts[k].tobytes() == (x * c).tobytes(), (k, cnt)
+            continue
+        prod32 = (x * cf).astype(np.float32)             # x and (float)c have 24 bits each: one rounding
+        if dtype == "float":
+            assert parts[k].tobytes() == prod32.tobytes(), (k, cnt)
+            continue
+        got = parts[k].view(np.uint16)
+        two, one = H.from_f32(prod32, dtype), round_once(x * c, dtype)
+        assert got.tobytes() == two.tobytes(), (k, cnt)
+        same = two == one
+        assert np.array_equal(got[same], one[same])
+        # same sign, finite: the patterns are ordered like the magnitudes
+        assert (np.abs(got.astype(np.int32) - one.astype(np.int32)) <= 1).all(), (k, cnt)
+        agree, total = agree + int(same.sum()), total + cnt
+    if dtype in H.TYPES:
+        print(f"{dtype}: two roundings equal the single one on {agree} of {total} elements")
+        assert 0.9 * total < agree
+
+
 # ---- the collectives over loopback ranks ---------------------------------------------------
 
 def rank_buckets(dtype, P, seed):

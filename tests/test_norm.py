@@ -251,6 +251,26 @@ def test_python_resolution():
     with pytest.raises(BineError) as ei:
         pico_amd.clip_multi("bine_lat", ts, "float", none, 2.0, stats=0x20000, stream=0)
     assert ei.value.status == ERR_ARG                                   # comm == NULL
+    # scale=False (norm_multi, then clip_segments on an empty list): max_norm and eps are refused
+    # first, then norm_multi's refusals in its order
+    for kw in (dict(max_norm=-2.0), dict(max_norm=float("nan")), dict(max_norm=2.0, eps=-1.0)):
+        with pytest.raises(BineError) as ei:
+            pico_amd.clip_multi(999, ts, "float", none, stats=0x20000, stream=0, scale=False, **kw)
+        assert ei.value.status == ERR_ARG
+        with pytest.raises(BineError) as ei:
+            pico_amd.loopback_clip_multi([none] * 2, 999, [ts, ts], "float", kw["max_norm"], kw.get("eps", 0.0),
+                                         [0x20000, 0x30000], scale=False)
+        assert ei.value.status == ERR_ARG
+    with pytest.raises(BineError) as ei:
+        pico_amd.clip_multi(999, ts, "float", none, 2.0, stats=0x20000, stream=0, scale=False)
+    assert ei.value.status == ERR_UNSUPPORTED
+    with pytest.raises(BineError) as ei:
+        pico_amd.clip_multi("bine_lat", ts + [FakeTensor(3, 0)], "float", none, 2.0, stats=0x20000, stream=0,
+                            scale=False)
+    assert ei.value.status == ERR_ARG                                   # a NULL tensor with elements
+    with pytest.raises(BineError) as ei:
+        pico_amd.clip_multi("bine_lat", ts, "float", none, 2.0, stats=0x20000, stream=0, scale=False)
+    assert ei.value.status == ERR_ARG                                   # comm == NULL
     with pytest.raises(ValueError):
         pico_amd.loopback_norm_multi([none] * 2, "bine_lat", [ts, ts[:2]], "float", [0x20000, 0x30000])
     with pytest.raises(ValueError):

@@ -12,7 +12,8 @@ peer-memory transport the flat one -- for float and bfloat16, bine_lat:
   clip_multi: stats[0..n] as norm_multi's, stats[n + 1] = numpy float64's
     min(1, max_norm / (sqrt(stats[n]) + eps)) bit for bit and the same on every
     rank, every tensor = bine_scale by that coefficient, the bytes around the
-    tensors untouched;
+    tensors untouched; before it clip_multi(scale=False): the same statistics
+    and coefficient, the tensors and the bytes around them untouched;
   graph mode (RCCL literal): norm_multi twice on the same buffers -- the second
     call replays (graphs_cached() unchanged) and gives the same bits.
 usage: python tools/norm_check.py [P]   (exit 0 = every rank, every case ok)
@@ -30,7 +31,7 @@ FORMS = (("rccl literal", False, False), ("rccl flat", False, True), ("direct fl
 TYPES = ("float", "bfloat16")
 ALGO = "bine_lat"
 MAX_NORM, EPS = 5.0, 1e-6
-CASES = len(FORMS) * len(TYPES) * 2 + 1
+CASES = len(FORMS) * len(TYPES) * 3 + 1
 
 
 def worker(rank, P, port, q):
@@ -121,8 +122,20 @@ def worker(rank, P, port, q):
                 bad.append(f"{form} norm_multi {dt}: the tensors or the bytes around them changed")
             else:
                 n_ok += 1
-            # clip_multi on the same tensors; the reference: bine_scale per tensor on a copy
             c = coef(want[n])
+            # the coefficient alone: clip_multi(scale=False) leaves the tensors as they are
+            stats0 = torch.full((n + 2,), -1.0, dtype=torch.float64, device="cuda")
+            run(lambda: pico_amd.clip_multi(ALGO, ptrs, dt, comm, MAX_NORM, EPS, counts=counts, stats=stats0,
+                                            scale=False))
+            got = stats0.cpu().numpy()
+            what = f"{form} clip_multi(scale=False) {dt}"
+            if got[:n + 1].tobytes() != want.tobytes() or got[n + 1].tobytes() != c.tobytes():
+                bad.append(f"{what}: stats or coefficient {got[n + 1]!r} for {c!r}")
+            elif not np.array_equal(t.cpu().numpy(), host):
+                bad.append(f"{what}: the tensors or the bytes around them changed")
+            else:
+                n_ok += 1
+            # clip_multi on the same tensors; the reference: bine_scale per tensor on a copy
             ref = t.clone()
             for cnt, f in zip(counts, off):
                 if cnt:
