@@ -492,6 +492,91 @@ int bine_adamw_segments(int n, void *const *p, void *const *m, void *const *v, c
 int64_t bine_plan_adamw(int n, const uint64_t *p, const uint64_t *m, const uint64_t *v, const uint64_t *g,
                         const uint64_t *pout, const size_t *counts, int gdtype, int odtype, uint64_t *out,
                         int64_t cap);
+/* ---- dynamic loss scaling: the step state and the skipping AdamW step -----------
+ * float16 training multiplies the loss by a scale S, so the stored gradient is
+ * g_true * S, and must skip the optimizer step when any gradient element on
+ * any rank overflowed.  Here the decision, the loss scale and the optimizer's
+ * step count live in device memory; the host decides nothing and waits for
+ * nothing.  The detection is bine_norm_multi's stats[n]: a binary64 sum of
+ * squares of float / float16 / bfloat16 values is finite exactly when every
+ * element on every rank is (a finite square is at most about 1.2e77), and its
+ * bits are the same on every rank, so every rank takes the same decision.
+ *
+ * The state block: BINE_STEP_STATE_BYTES bytes, 8-byte aligned, plain data --
+ * eight doubles d[0..7], then eight floats c[0..7]:
+ *   d[0] scale    the loss scale the NEXT backward pass multiplies the loss by
+ *   d[1] good     updates without overflow since the scale last changed
+ *   d[2] step     optimizer steps taken
+ *   d[3] pw1      running product of the taken steps' beta1 (beta1^step)
+ *   d[4] pw2      likewise of beta2
+ *   d[5] skip     0.0 or 1.0, set by the latest update
+ *   d[6] gm       the latest update's gradient multiplier (0.0 when skipped)
+ *   d[7] skipped  total skipped steps
+ *   c[0..7]       the latest TAKEN step's constants, bine_adamw_consts' order
+ * Counts are whole numbers held in doubles.  Saving and restoring the state is
+ * copying its bytes.
+ *
+ * The update (bine_step_update on the device, bine_step_update_host its twin:
+ * one statement compiled for both, pico_amd/csrc/bine_internal.h), every
+ * operation binary64 and correctly rounded, nothing contracted, n2 = *norm2:
+ *   if !(n2 <= DBL_MAX):                                  (+inf or NaN)
+ *     skip = 1; gm = 0; skipped += 1; good = 0
+ *     scale = max(scale * backoff_factor, min_scale)
+ *   else:
+ *     inv = 1 / scale
+ *     nrm = sqrt(n2) * inv                                (the true gradient's norm)
+ *     r = max_norm / (nrm + clip_eps);  cc = r < 1 ? r : 1
+ *                   (bine_clip_segments' rule; max_norm = +inf: no clipping)
+ *     gm = cc * inv
+ *     step += 1;  pw1 = pw1 * beta1;  pw2 = pw2 * beta2
+ *     c[] = (float) of 1 - lr * weight_decay, beta1, 1 - beta1, beta2, 1 - beta2,
+ *           1 / sqrt(1 - pw2), eps, lr / (1 - pw1)
+ *     skip = 0;  good += 1
+ *     if good >= growth_interval:  scale = min(scale * growth_factor, max_scale);  good = 0
+ * A skipped update leaves step, pw1, pw2 and c[] as they were.  The running
+ * products stand in for pow(beta, step), which differs between host and
+ * device: after t steps their relative error is at most t * 2^-53, so c[5]
+ * and c[7] are within one binary32 ulp of bine_adamw_consts at the same step
+ * (equal at step 1) and the other six constants are equal.
+ * bine_step_state_init (host only): scale, good = 0, step, pw1 and pw2 formed by
+ * `step` sequential multiplications from 1.0 (the product the updates form;
+ * it stops early once neither product changes any more), everything else 0;
+ * step = 0 is the fresh state.  BINE_ERR_ARG: host_state NULL or not 8-byte
+ * aligned; scale not finite or not positive; step < 0; a beta outside [0, 1)
+ * or NaN.
+ * bine_step_update: state and norm2 are device pointers; ONE launch of
+ * k_step_update (thread 0 runs the rule, the hyper-parameters by value),
+ * stream-ordered, no host synchronization; an ordinary launch, never captured.
+ * BINE_ERR_ARG, before any HIP call, in this order: hyper NULL; the refusals of
+ * bine_adamw_consts for lr, beta1, beta2, eps and weight_decay; max_norm or
+ * clip_eps negative or NaN; growth_factor not finite or below 1;
+ * backoff_factor outside (0, 1]; growth_interval < 1; not 0 < min_scale <=
+ * max_scale < inf; state or norm2 NULL or not 8-byte aligned
+ * (bine_step_update_host: host_state; norm2 is a value).
+ *
+ * bine_adamw_segments_dyn: bine_adamw_segments with the multiplier, the
+ * constants and a skip flag read from `state` (device) by every workgroup:
+ *   skip != 0: no store at all -- p, m, v and pout keep every bit;
+ *   otherwise gm = (float)d[6] and the per-element lines of
+ *   bine_adamw_segments with c[0..7] as the constants.
+ * The same kernel (k_adamw_segs, its DYN form), tile table
+ * (bine_plan_adamw describes these launches too), bodies and stores; a full
+ * tile's loads are issued before the state is read.  BINE_ERR_ARG, before any
+ * HIP call: the list checks of bine_adamw_segments (through pout), then state
+ * NULL or not 8-byte aligned. */
+#define BINE_STEP_STATE_BYTES 96
+typedef struct bine_step_hyper {
+  double lr, beta1, beta2, eps, weight_decay;
+  double max_norm, clip_eps;
+  double growth_factor, backoff_factor, min_scale, max_scale;
+  int64_t growth_interval;
+} bine_step_hyper;
+int bine_step_state_init(void *host_state, double scale, int64_t step, double beta1, double beta2);
+int bine_step_update_host(void *host_state, double norm2, const bine_step_hyper *hyper);
+int bine_step_update(void *state, const double *norm2, const bine_step_hyper *hyper, void *stream);
+int bine_adamw_segments_dyn(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                            void *const *pout, const size_t *counts, int gdtype, int odtype, const void *state,
+                            void *stream);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -960,6 +1045,16 @@ int bine_adamw_multi(bine_comm_t comm, int ag_algo, int n, void *const *params, 
                      void *const *v, const void *const *g, const size_t *shard_counts, int gdtype, int odtype,
                      double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
                      const double *gcoef, double grad_mul, void *stream);
+/* The dynamic form: bine_adamw_segments_dyn with pout[k] = params[k] + rank *
+ * shard_counts[k], then the same in-place bine_allgather_multi.  On a skipped
+ * step the allgather still runs -- the host does not know -- and gathers the
+ * slots as they stand: params must hold the CURRENT parameters (every rank's
+ * slot = narrow(p)) before the first call, or a first call that skips spreads
+ * whatever the slots held.  Refusals as bine_adamw_multi, with
+ * bine_adamw_segments_dyn's in place of bine_adamw_segments'. */
+int bine_adamw_multi_dyn(bine_comm_t comm, int ag_algo, int n, void *const *params, void *const *p, void *const *m,
+                         void *const *v, const void *const *g, const size_t *shard_counts, int gdtype, int odtype,
+                         const void *state, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -1063,6 +1158,11 @@ int bine_loopback_run_adamw_multi(bine_comm_t *comms, int nranks, int ag_algo, i
                                   const size_t *shard_counts, int gdtype, int odtype, double lr, double beta1,
                                   double beta2, double eps, double weight_decay, int64_t step,
                                   const double *const *gcoef, double grad_mul, int *statuses);
+/* bine_adamw_multi_dyn on every virtual rank: states one device pointer per rank */
+int bine_loopback_run_adamw_multi_dyn(bine_comm_t *comms, int nranks, int ag_algo, int n, void *const *params,
+                                      void *const *p, void *const *m, void *const *v, const void *const *g,
+                                      const size_t *shard_counts, int gdtype, int odtype,
+                                      const void *const *states, int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

@@ -50,6 +50,15 @@ wants it), bit for bit a float32 statement of one operation per line;
 ``adamw_multi`` adds the in-place ``allgather_multi`` of the full parameters.
 ``adamw_consts`` and ``plan_adamw`` are the host views of its constants and
 launches.
+
+Dynamic loss scaling: a 96-byte step state in device memory (``step_state_init``)
+carries the loss scale and the step count.  ``step_update`` updates it on the
+device from ``norm_multi``'s global squared norm -- infinite or NaN: skip and
+back off; else the multiplier (clip / scale) and the step's constants --
+and ``adamw_segments_dyn`` / ``adamw_multi_dyn`` take everything from it, storing
+nothing on a skipped step: no host decision, no synchronization.
+``step_update_host`` is the update's host twin, ``step_state_read`` the state as
+a dict (it synchronizes).
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

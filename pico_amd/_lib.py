@@ -80,6 +80,17 @@ class OpTime(ctypes.Structure):
                 ("start_ms", ctypes.c_float), ("ms", ctypes.c_float)]
 
 
+# the step state of bine_step_update (BINE_STEP_STATE_BYTES: 8 doubles, 8 floats)
+STEP_STATE_BYTES = 96
+
+
+class StepHyper(ctypes.Structure):
+    """bine_step_hyper"""
+    _fields_ = [(k, ctypes.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm", "clip_eps",
+                                               "growth_factor", "backoff_factor", "min_scale", "max_scale")]
+    _fields_.append(("growth_interval", ctypes.c_int64))
+
+
 PRIM_NAMES = {1: "SEND", 2: "RECV", 3: "REDUCE", 4: "REDUCE3", 5: "COPY", 6: "REDUCE_TREE", 7: "SCALE"}
 # bine_prim_t.flags
 PRIM_PIPELINE, PRIM_SCALED, PRIM_WIDE = 1, 2, 4
@@ -197,6 +208,12 @@ def lib():
         "bine_adamw_multi": ([vp, i, i, vp, vp, vp, vp, vp, vp, i, i, d, d, d, d, d, ctypes.c_int64, vp, d, vp], i),
         "bine_loopback_run_adamw_multi": ([vp, i, i, i, vp, vp, vp, vp, vp, vp, i, i, d, d, d, d, d, ctypes.c_int64,
                                            vp, d, vp], i),
+        "bine_step_state_init": ([vp, d, ctypes.c_int64, d, d], i),
+        "bine_step_update_host": ([vp, d, vp], i),
+        "bine_step_update": ([vp, vp, vp, vp], i),
+        "bine_adamw_segments_dyn": ([i, vp, vp, vp, vp, vp, vp, i, i, vp, vp], i),
+        "bine_adamw_multi_dyn": ([vp, i, i, vp, vp, vp, vp, vp, vp, i, i, vp, vp], i),
+        "bine_loopback_run_adamw_multi_dyn": ([vp, i, i, i, vp, vp, vp, vp, vp, vp, i, i, vp, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

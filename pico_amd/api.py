@@ -927,6 +927,131 @@ def loopback_adamw_multi(comms, ag_algo, params, p, m, v, g, lr: float = 1e-3, b
     return rc, list(st)
 
 
+# ---- dynamic loss scaling: the step state and the skipping AdamW step ----------------------
+
+STEP_STATE_FIELDS = ("scale", "good", "step", "pw1", "pw2", "skip", "gm", "skipped")
+
+
+def _step_hyper(lr, beta1, beta2, eps, weight_decay, max_norm, clip_eps, growth_factor, backoff_factor,
+                growth_interval, min_scale, max_scale):
+    return _lib.StepHyper(float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), float(max_norm),
+                          float(clip_eps), float(growth_factor), float(backoff_factor), float(min_scale),
+                          float(max_scale), int(growth_interval))
+
+
+def step_state_init(scale: float = 65536.0, step: int = 0, beta1: float = 0.9, beta2: float = 0.999):
+    """A fresh step state (bine_step_state_init, host only): a numpy uint8 array of
+    96 bytes -- eight float64 (scale, good, step, pw1, pw2, skip, gm, skipped) and
+    eight float32 (the latest taken step's adamw_consts).  step > 0 resumes after
+    that many taken steps: pw1 = beta1^step and pw2 = beta2^step as `step`
+    sequential float64 multiplications.  Copy it to the device (any 8-byte
+    aligned 96 bytes) for step_update / adamw_segments_dyn; saving and restoring
+    a state is copying its bytes."""
+    import numpy as np
+    buf = np.zeros(_lib.STEP_STATE_BYTES // 8, dtype=np.float64)     # 8-byte aligned
+    check(lib().bine_step_state_init(buf.ctypes.data, float(scale), int(step), float(beta1), float(beta2)),
+          "bine_step_state_init")
+    return buf.view(np.uint8)
+
+
+def step_update_host(state, norm2: float, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
+                     eps: float = 1e-8, weight_decay: float = 0.01, max_norm: float = float("inf"),
+                     clip_eps: float = 1e-6, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                     growth_interval: int = 2000, min_scale: float = 1.0, max_scale: float = 2.0 ** 24) -> None:
+    """step_update's host twin (bine_step_update_host): the same statement on a
+    numpy state block (96 bytes, 8-byte aligned, updated in place) and a host
+    float norm2."""
+    h = _step_hyper(lr, beta1, beta2, eps, weight_decay, max_norm, clip_eps, growth_factor, backoff_factor,
+                    growth_interval, min_scale, max_scale)
+    if state.nbytes != _lib.STEP_STATE_BYTES or not state.flags["C_CONTIGUOUS"] or not state.flags["WRITEABLE"]:
+        raise ValueError("step_update_host: state is not a writable block of 96 bytes")
+    check(lib().bine_step_update_host(state.ctypes.data, float(norm2), ctypes.byref(h)), "bine_step_update_host")
+
+
+def step_update(state, norm2, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                weight_decay: float = 0.01, max_norm: float = float("inf"), clip_eps: float = 1e-6,
+                growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000,
+                min_scale: float = 1.0, max_scale: float = 2.0 ** 24, stream=None) -> None:
+    """The loss-scale and step-count update on the device (bine_step_update, one
+    launch, stream-ordered, no host synchronization): `state` the 96-byte block
+    in device memory, `norm2` a device float64 -- norm_multi's stats[n:], the
+    squared norm of the SCALED gradient over all ranks.  norm2 infinite or NaN
+    (some element on some rank overflowed): skip = 1, the scale backs off, the
+    step count stays.  Otherwise the step counts, gm = min(1, max_norm /
+    (sqrt(norm2) / scale + clip_eps)) / scale, the step's adamw_consts are
+    formed from running products of the betas, and after growth_interval good
+    updates the scale grows.  Every operation float64 (include/bine_amd.h)."""
+    h = _step_hyper(lr, beta1, beta2, eps, weight_decay, max_norm, clip_eps, growth_factor, backoff_factor,
+                    growth_interval, min_scale, max_scale)
+    check(lib().bine_step_update(_ptr(state), _ptr(norm2), ctypes.byref(h), _stream(stream, None)),
+          "bine_step_update")
+
+
+def step_state_read(state) -> dict:
+    """The state's fields as a dict: scale, good, step, pw1, pw2, skip, gm, skipped
+    (Python floats) and consts (numpy float32 of 8).  A device tensor is copied
+    to the host, which SYNCHRONIZES with its stream: for logging and
+    checkpoints, not for the training loop."""
+    import numpy as np
+    if hasattr(state, "detach"):
+        state = state.detach().contiguous().cpu().numpy()
+    raw = np.ascontiguousarray(state).view(np.uint8).reshape(-1)
+    if raw.size != _lib.STEP_STATE_BYTES:
+        raise ValueError("step_state_read: state is not a block of 96 bytes")
+    d = raw[:64].copy().view(np.float64)
+    out = {k: float(x) for k, x in zip(STEP_STATE_FIELDS, d)}
+    out["consts"] = raw[64:].copy().view(np.float32)
+    return out
+
+
+def adamw_segments_dyn(p, m, v, g, state, pout=None, gdtype=None, odtype=None, counts=None, stream=None) -> None:
+    """adamw_segments with everything but the tensors read from the device
+    state step_update left (bine_adamw_segments_dyn): skip != 0 stores nothing
+    -- p, m, v and pout keep every bit -- otherwise gm = float32(state gm) and
+    the state's eight constants.  No hyper-parameter, no step number and no
+    decision on the host."""
+    c = _adamw_lists("adamw_segments_dyn", p, m, v, g, pout, counts)
+    check(lib().bine_adamw_segments_dyn(len(p), _ptrs(p), _ptrs(m), _ptrs(v), _ptrs(g),
+                                        None if pout is None else _ptrs(pout), c, _adamw_dtype(gdtype, g),
+                                        _adamw_dtype(odtype, pout), _ptr(state), _stream(stream, None)),
+          "bine_adamw_segments_dyn")
+
+
+def adamw_multi_dyn(ag_algo, params, p, m, v, g, state, comm: Comm, gdtype=None, odtype=None, shard_counts=None,
+                    stream=None) -> None:
+    """bine_adamw_multi_dyn: adamw_segments_dyn into this rank's slot of every
+    params[k], then allgather_multi in place.  The allgather runs after a
+    skipped step too (the host does not know) and gathers the slots as they
+    stand, so params must hold the current parameters before the first call."""
+    c = _adamw_lists("adamw_multi_dyn", p, m, v, g, params, shard_counts)
+    check(lib().bine_adamw_multi_dyn(comm.handle, _algo("allgather", ag_algo), len(p), _ptrs(params), _ptrs(p),
+                                     _ptrs(m), _ptrs(v), _ptrs(g), c, _adamw_dtype(gdtype, g),
+                                     _adamw_dtype(odtype, params), _ptr(state), _stream(stream, comm)),
+          f"adamw_multi_dyn ({ag_algo})")
+
+
+def loopback_adamw_multi_dyn(comms, ag_algo, params, p, m, v, g, states, gdtype=None, odtype=None,
+                             shard_counts=None):
+    """adamw_multi_dyn on every virtual rank: lists as loopback_adamw_multi,
+    states one device block per rank.  Returns (status, per-rank statuses)."""
+    P = len(comms)
+    n = len(p[0])
+    if any(len(x) != P for x in (params, p, m, v, g, states)) or \
+            any(len(r) != n for x in (params, p, m, v, g) for r in x):
+        raise ValueError("loopback_adamw_multi_dyn: the ranks' lists differ in length")
+    if shard_counts is None:
+        shard_counts = [[t.numel() for t in r] for r in p]
+    flat = lambda x: [t for r in x for t in r]  # noqa: E731
+    fc = flat(shard_counts)
+    st = (ctypes.c_int * P)()
+    hs = (ctypes.c_void_p * P)(*[c.handle.value for c in comms])
+    rc = lib().bine_loopback_run_adamw_multi_dyn(
+        hs, P, _algo("allgather", ag_algo), n, _ptrs(flat(params)), _ptrs(flat(p)), _ptrs(flat(m)), _ptrs(flat(v)),
+        _ptrs(flat(g)), (ctypes.c_size_t * max(len(fc), 1))(*fc), _adamw_dtype(gdtype, flat(g)),
+        _adamw_dtype(odtype, flat(params)), _ptrs(states), st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -1320,6 +1445,8 @@ __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fus
            "sumsq_segments", "plan_sumsq", "clip_segments", "norm_multi", "clip_multi", "loopback_norm_multi",
            "loopback_clip_multi",
            "adamw_consts", "plan_adamw", "adamw_segments", "adamw_multi", "loopback_adamw_multi",
+           "step_state_init", "step_update_host", "step_update", "step_state_read", "adamw_segments_dyn",
+           "adamw_multi_dyn", "loopback_adamw_multi_dyn",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

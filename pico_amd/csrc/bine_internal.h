@@ -318,6 +318,74 @@ int launch_adamw_segments_h16(int n, void *const *p, void *const *m, void *const
                               void *const *pout, const size_t *counts, int gdtype, int odtype, double lr,
                               double beta1, double beta2, double eps, double weight_decay, int64_t step,
                               const double *gcoef, double grad_mul, void *stream);
+
+// dynamic loss scaling (bine_step_update, bine_adamw_segments_dyn): the state
+// block of bine_amd.h as a struct, and its update rule -- ONE statement for the
+// host twin (segments.cpp: plain C++) and for k_step_update (kernels.hip:
+// thread 0).  Every operation is binary64 and correctly rounded, one per
+// expression node; both compilations pass -ffp-contract=off, so no product
+// folds into a sum.  tests/step_sim.py restates it in numpy.
+struct StepState {
+  double d[8];  // scale, good, step, pw1, pw2, skip, gm, skipped
+  float c[8];   // bine_adamw_consts' order
+};
+static_assert(sizeof(StepState) == BINE_STEP_STATE_BYTES && alignof(StepState) == 8, "bine_amd.h's layout");
+#if defined(__HIPCC__)
+#define BINE_HOST_DEVICE __attribute__((host)) __attribute__((device))
+#else
+#define BINE_HOST_DEVICE
+#endif
+BINE_HOST_DEVICE inline void step_update_rule(StepState *s, double n2, const bine_step_hyper &h) {
+  double scale = s->d[0];
+  if (!(n2 <= 1.7976931348623157e308)) {  // +inf or NaN: some element on some rank was not finite
+    s->d[5] = 1.0;
+    s->d[6] = 0.0;
+    s->d[7] = s->d[7] + 1.0;
+    s->d[1] = 0.0;
+    scale = scale * h.backoff_factor;
+    s->d[0] = scale > h.min_scale ? scale : h.min_scale;
+    return;
+  }
+  const double inv = 1.0 / scale;
+  const double nrm = __builtin_sqrt(n2) * inv;
+  const double r = h.max_norm / (nrm + h.clip_eps);
+  const double cc = r < 1.0 ? r : 1.0;  // a NaN r gives 1.0, as bine_clip_segments
+  s->d[6] = cc * inv;
+  s->d[2] = s->d[2] + 1.0;
+  const double pw1 = s->d[3] * h.beta1, pw2 = s->d[4] * h.beta2;
+  s->d[3] = pw1;
+  s->d[4] = pw2;
+  s->c[0] = (float)(1.0 - h.lr * h.weight_decay);
+  s->c[1] = (float)h.beta1;
+  s->c[2] = (float)(1.0 - h.beta1);
+  s->c[3] = (float)h.beta2;
+  s->c[4] = (float)(1.0 - h.beta2);
+  s->c[5] = (float)(1.0 / __builtin_sqrt(1.0 - pw2));
+  s->c[6] = (float)h.eps;
+  s->c[7] = (float)(h.lr / (1.0 - pw1));
+  s->d[5] = 0.0;
+  const double good = s->d[1] + 1.0;
+  if (good >= (double)h.growth_interval) {
+    scale = scale * h.growth_factor;
+    s->d[0] = scale < h.max_scale ? scale : h.max_scale;
+    s->d[1] = 0.0;
+  } else {
+    s->d[1] = good;
+  }
+}
+// the hyper-parameters' refusals, then state / norm2 NULL or not 8-byte aligned
+// (bine_step_update_host: norm2 is a value, pass any aligned non-NULL address)
+int step_update_args(const void *state, const void *norm2, const bine_step_hyper *h);
+// bine_step_update: step_update_args, then one launch of k_step_update
+int launch_step_update_h16(void *state, const double *norm2, const bine_step_hyper *h, void *stream);
+// bine_adamw_segments_dyn's checks: adamw_args' list checks, then the state
+// pointer (NULL or not 8-byte aligned)
+int adamw_dyn_args(int n, void *const *p, void *const *m, void *const *v, const void *const *g, void *const *pout,
+                   const size_t *counts, int gdtype, int odtype, const void *state, std::vector<AdamwLaunch> *ls);
+// bine_adamw_segments_dyn: adamw_dyn_args, then k_adamw_segs' DYN form per launch
+int launch_adamw_segments_dyn_h16(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                                  void *const *pout, const size_t *counts, int gdtype, int odtype, const void *state,
+                                  void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -2067,6 +2067,16 @@ int bine_adamw_segments(int n, void *const *p, void *const *m, void *const *v, c
                                    step, gcoef, grad_mul, stream);  // checks its arguments
 }
 
+int bine_step_update(void *state, const double *norm2, const bine_step_hyper *hyper, void *stream) {
+  return launch_step_update_h16(state, norm2, hyper, stream);  // likewise
+}
+
+int bine_adamw_segments_dyn(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                            void *const *pout, const size_t *counts, int gdtype, int odtype, const void *state,
+                            void *stream) {
+  return launch_adamw_segments_dyn_h16(n, p, m, v, g, pout, counts, gdtype, odtype, state, stream);  // likewise
+}
+
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream) {
   return launch_fill_pico(buf, count, dtype, seed, stream);
 }
@@ -2732,6 +2742,31 @@ int bine_adamw_multi(bine_comm_t c, int ag_algo, int n, void *const *params, voi
   return bine_allgather_multi(c, ag_algo, n, nullptr, params, shard_counts, odtype, stream);
 }
 
+// the dynamic form's checks: bine_adamw_segments_dyn's with params in pout's place
+static int adamw_multi_dyn_args(int ag_algo, int n, void *const *params, void *const *p, void *const *m,
+                                void *const *v, const void *const *g, const size_t *shard_counts, int gdtype,
+                                int odtype, const void *state) {
+  if (const int rc = adamw_dyn_args(n, p, m, v, g, params, shard_counts, gdtype, odtype, state, nullptr)) return rc;
+  return shard_args(false, ag_algo, n, nullptr, params, shard_counts, odtype, 0, 1.0, 0);
+}
+
+int bine_adamw_multi_dyn(bine_comm_t c, int ag_algo, int n, void *const *params, void *const *p, void *const *m,
+                         void *const *v, const void *const *g, const size_t *shard_counts, int gdtype, int odtype,
+                         const void *state, void *stream) {
+  if (const int rc = adamw_multi_dyn_args(ag_algo, n, params, p, m, v, g, shard_counts, gdtype, odtype, state))
+    return rc;
+  if (!c) return BINE_ERR_ARG;
+  const size_t osz = adamw_esz(odtype);
+  std::vector<void *> pout((size_t)n);
+  for (int k = 0; k < n; k++)
+    pout[k] = shard_counts[k] ? (char *)params[k] + (size_t)c->rank * shard_counts[k] * osz : nullptr;
+  if (const int rc = launch_adamw_segments_dyn_h16(n, p, m, v, g, pout.data(), shard_counts, gdtype, odtype, state,
+                                                   stream))
+    return rc;
+  // also after a skipped step, which the host cannot know of: the slots as they stand
+  return bine_allgather_multi(c, ag_algo, n, nullptr, params, shard_counts, odtype, stream);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -3061,6 +3096,27 @@ int bine_loopback_run_adamw_multi(bine_comm_t *comms, int nranks, int ag_algo, i
     return bine_adamw_multi(comms[r], ag_algo, n, at(params, r), at(p, r), at(m, r), at(v, r), at(g, r),
                             at(shard_counts, r), gdtype, odtype, lr, beta1, beta2, eps, weight_decay, step,
                             gcoef ? gcoef[r] : nullptr, grad_mul, comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_adamw_multi_dyn(bine_comm_t *comms, int nranks, int ag_algo, int n, void *const *params,
+                                      void *const *p, void *const *m, void *const *v, const void *const *g,
+                                      const size_t *shard_counts, int gdtype, int odtype,
+                                      const void *const *states, int *statuses) {
+  auto at = [&](auto *list, int r) { return list && n > 0 ? list + (size_t)r * n : list; };
+  // before any thread, stream or HIP call: what a rank would refuse without a communicator
+  int bad = states ? BINE_SUCCESS : BINE_ERR_ARG;
+  for (int r = 0; !bad && r < nranks; r++)
+    bad = adamw_multi_dyn_args(ag_algo, n, at(params, r), at(p, r), at(m, r), at(v, r), at(g, r),
+                               at(shard_counts, r), gdtype, odtype, states[r]);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return bad;
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_adamw_multi_dyn(comms[r], ag_algo, n, at(params, r), at(p, r), at(m, r), at(v, r), at(g, r),
+                                at(shard_counts, r), gdtype, odtype, states[r], comms[r]->stream);
   });
 }
 

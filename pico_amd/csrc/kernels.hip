@@ -2060,6 +2060,7 @@ struct AdamwSegs {
   double grad_mul;
   float c[8];  // bine_adamw_consts: dk, b1, 1 - b1, b2, 1 - b2, rbc2, eps, ss
   AdamwSeg s[kAdamwSegsPerLaunch];
+  const StepState *state;  // the DYN form's skip flag, multiplier and constants (last: s[] keeps its offsets)
 };
 static_assert(sizeof(AdamwSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
 
@@ -2124,7 +2125,12 @@ __device__ __forceinline__ void adamw_vec(u32x4 xp, u32x4 xm, u32x4 xv, vec4_of<
   }
 }
 
-template <typename G, typename O, bool PO>
+// DYN (bine_adamw_segments_dyn): where the plain form reads *gcoef, every
+// workgroup reads skip, gm and the eight constants from a.state (what
+// k_step_update left there) -- after a full tile's loads are issued, so the
+// state's latency hides behind them.  skip != 0: the workgroup returns before
+// its first store.  a.gcoef, a.grad_mul and a.c are not read.
+template <typename G, typename O, bool PO, bool DYN = false>
 __global__ __launch_bounds__(kBlock) void k_adamw_segs(AdamwSegs a) {
   using GV = vec4_of<G>;
   using OV = vec4_of<O>;
@@ -2154,12 +2160,25 @@ __global__ __launch_bounds__(kBlock) void k_adamw_segs(AdamwSegs a) {
       xg[u] = vg[i];
     }
   }
-  // gm = (float)(c * grad_mul): the product in binary64, one rounding
-  const double cf = a.gcoef ? *a.gcoef : 1.0;
-  const float gm = (float)(cf * a.grad_mul);
+  float gm;
+  [[maybe_unused]] float cd[8];
+  if constexpr (DYN) {
+    if (a.state->d[5] != 0.0) return;  // workgroup-uniform: a skipped step stores nothing
+    gm = (float)a.state->d[6];
+#pragma unroll
+    for (int j = 0; j < 8; j++) cd[j] = a.state->c[j];
+  } else {
+    // gm = (float)(c * grad_mul): the product in binary64, one rounding
+    const double cf = a.gcoef ? *a.gcoef : 1.0;
+    gm = (float)(cf * a.grad_mul);
+  }
+  const float(&c)[8] = *[&]() -> const float(*)[8] {
+    if constexpr (DYN) return &cd;
+    else return &a.c;
+  }();
   auto one = [&](size_t i) {
     float pp = p[i], mm = m[i], vx = v[i];
-    adamw1(pp, mm, vx, adamw_widen<G>(g[i]), gm, a.c);
+    adamw1(pp, mm, vx, adamw_widen<G>(g[i]), gm, c);
     p[i] = pp;
     m[i] = mm;
     v[i] = vx;
@@ -2172,12 +2191,12 @@ __global__ __launch_bounds__(kBlock) void k_adamw_segs(AdamwSegs a) {
   if (full) {
 #pragma unroll
     for (int u = 0; u < kScaleU; u++)
-      adamw_vec<G, O, PO, true>(xp[u], xm[u], xv[u], xg[u], gm, a.c, vp, vm, vv, vo, base + (size_t)u * kBlock);
+      adamw_vec<G, O, PO, true>(xp[u], xm[u], xv[u], xg[u], gm, c, vp, vm, vv, vo, base + (size_t)u * kBlock);
   } else if (!elem) {
 #pragma unroll
     for (int u = 0; u < kScaleU; u++) {
       const size_t i = base + (size_t)u * kBlock;
-      if (i < nvec) adamw_vec<G, O, PO, false>(vp[i], vm[i], vv[i], vg[i], gm, a.c, vp, vm, vv, vo, i);
+      if (i < nvec) adamw_vec<G, O, PO, false>(vp[i], vm[i], vv[i], vg[i], gm, c, vp, vm, vv, vo, i);
     }
   } else {  // the tile's elements one by one
     const size_t lo = he + (size_t)wt * kBlock * kScaleU * 4, end = he + nvec * 4;
@@ -2197,17 +2216,11 @@ static int with_adamw_dtype(int dtype, F &&f) {
   }
 }
 
-int launch_adamw_segments_h16(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
-                              void *const *pout, const size_t *counts, int gdtype, int odtype, double lr,
-                              double beta1, double beta2, double eps, double weight_decay, int64_t step,
-                              const double *gcoef, double grad_mul, void *stream) {
-  AdamwSegs a;
-  std::vector<AdamwLaunch> ls;
-  if (const int rc = adamw_args(n, p, m, v, g, pout, counts, gdtype, odtype, lr, beta1, beta2, eps, weight_decay,
-                                step, gcoef, grad_mul, a.c, &ls))
-    return rc;
-  a.gcoef = gcoef;
-  a.grad_mul = grad_mul;
+// k_adamw_segs per launch of `ls`; a.gcoef / grad_mul / c (plain) or a.state (DYN) are the caller's
+template <bool DYN>
+static int adamw_issue(AdamwSegs &a, const std::vector<AdamwLaunch> &ls, void *const *p, void *const *m,
+                       void *const *v, const void *const *g, void *const *pout, const size_t *counts, int gdtype,
+                       int odtype, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   return with_adamw_dtype(gdtype, [&](auto gtag) {
     using G = typename decltype(gtag)::type;
@@ -2225,13 +2238,56 @@ int launch_adamw_segments_h16(int n, void *const *p, void *const *m, void *const
         for (int s = L.nseg; s < kAdamwSegsPerLaunch; s++) a.s[s] = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
         const dim3 grid(L.tile0[L.nseg]), blk(kBlock);
         // without pout one instantiation per G serves every odtype
-        if (pout) hipLaunchKernelGGL((k_adamw_segs<G, O, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((k_adamw_segs<G, float, false>), grid, blk, 0, st, a);
+        if (pout) hipLaunchKernelGGL((k_adamw_segs<G, O, true, DYN>), grid, blk, 0, st, a);
+        else hipLaunchKernelGGL((k_adamw_segs<G, float, false, DYN>), grid, blk, 0, st, a);
         if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
       }
       return BINE_SUCCESS;
     });
   });
+}
+
+int launch_adamw_segments_h16(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                              void *const *pout, const size_t *counts, int gdtype, int odtype, double lr,
+                              double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                              const double *gcoef, double grad_mul, void *stream) {
+  AdamwSegs a;
+  std::vector<AdamwLaunch> ls;
+  if (const int rc = adamw_args(n, p, m, v, g, pout, counts, gdtype, odtype, lr, beta1, beta2, eps, weight_decay,
+                                step, gcoef, grad_mul, a.c, &ls))
+    return rc;
+  a.gcoef = gcoef;
+  a.grad_mul = grad_mul;
+  a.state = nullptr;
+  return adamw_issue<false>(a, ls, p, m, v, g, pout, counts, gdtype, odtype, stream);
+}
+
+int launch_adamw_segments_dyn_h16(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                                  void *const *pout, const size_t *counts, int gdtype, int odtype, const void *state,
+                                  void *stream) {
+  AdamwSegs a;
+  std::vector<AdamwLaunch> ls;
+  if (const int rc = adamw_dyn_args(n, p, m, v, g, pout, counts, gdtype, odtype, state, &ls)) return rc;
+  a.gcoef = nullptr;
+  a.grad_mul = 0.0;
+  for (float &x : a.c) x = 0.0f;
+  a.state = static_cast<const StepState *>(state);
+  return adamw_issue<true>(a, ls, p, m, v, g, pout, counts, gdtype, odtype, stream);
+}
+
+// k_step_update: the loss-scale / step-count update of bine_step_update
+// (bine_amd.h), one thread running step_update_rule (bine_internal.h) -- the
+// statement the host twin compiles -- on the global norm k_sumsq_total left in
+// device memory.
+__global__ __launch_bounds__(64) void k_step_update(StepState *s, const double *norm2, bine_step_hyper h) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) step_update_rule(s, *norm2, h);
+}
+
+int launch_step_update_h16(void *state, const double *norm2, const bine_step_hyper *h, void *stream) {
+  if (const int rc = step_update_args(state, norm2, h)) return rc;
+  hipLaunchKernelGGL(k_step_update, dim3(1), dim3(1), 0, (hipStream_t)stream, static_cast<StepState *>(state), norm2,
+                     *h);
+  return status(hipGetLastError());
 }
 #endif  // BINE_OPSET == 2
 

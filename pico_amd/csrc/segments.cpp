@@ -14,7 +14,10 @@
 // (tools/sumsq_check.cpp).  The fused AdamW step walks plan_norm_launches' table
 // over p and cuts it at kAdamwSegsPerLaunch descriptors: plan_adamw_launches /
 // bine_plan_adamw, with the step's constants (bine_adamw_consts) beside them
-// (tools/adamw_check.cpp).
+// (tools/adamw_check.cpp).  Dynamic loss scaling keeps its host half here too:
+// bine_step_state_init, the refusals (step_update_args, adamw_dyn_args) and
+// bine_step_update_host, the host compilation of the statement k_step_update
+// runs (step_update_rule, bine_internal.h; tools/step_check.cpp).
 #include <algorithm>
 #include <cmath>
 
@@ -180,10 +183,10 @@ int plan_adamw_launches(int n, const uint64_t *p, const uint64_t *m, const uint6
   return BINE_SUCCESS;
 }
 
-int adamw_args(int n, void *const *p, void *const *m, void *const *v, const void *const *g, void *const *pout,
-               const size_t *counts, int gdtype, int odtype, double lr, double beta1, double beta2, double eps,
-               double weight_decay, int64_t step, const double *gcoef, double grad_mul, float consts[8],
-               std::vector<AdamwLaunch> *ls) {
+// the list checks of bine_adamw_segments (through pout) and the launches
+static int adamw_list_args(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
+                           void *const *pout, const size_t *counts, int gdtype, int odtype,
+                           std::vector<AdamwLaunch> *ls) {
   if (!adamw_esz(gdtype) || !adamw_esz(odtype)) return BINE_ERR_ARG;
   if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!p || !m || !v || !g || !counts))) return BINE_ERR_ARG;
   std::vector<uint64_t> a((size_t)5 * (n > 0 ? n : 1));
@@ -193,16 +196,62 @@ int adamw_args(int n, void *const *p, void *const *m, void *const *v, const void
     ga[k] = (uint64_t)(uintptr_t)g[k], oa[k] = pout ? (uint64_t)(uintptr_t)pout[k] : 0;
   }
   std::vector<AdamwLaunch> local;
-  if (const int rc = plan_adamw_launches(n, pa, ma, va, ga, pout ? oa : nullptr, counts, gdtype, odtype,
-                                         ls ? *ls : local))
-    return rc;
+  return plan_adamw_launches(n, pa, ma, va, ga, pout ? oa : nullptr, counts, gdtype, odtype, ls ? *ls : local);
+}
+
+int adamw_args(int n, void *const *p, void *const *m, void *const *v, const void *const *g, void *const *pout,
+               const size_t *counts, int gdtype, int odtype, double lr, double beta1, double beta2, double eps,
+               double weight_decay, int64_t step, const double *gcoef, double grad_mul, float consts[8],
+               std::vector<AdamwLaunch> *ls) {
+  if (const int rc = adamw_list_args(n, p, m, v, g, pout, counts, gdtype, odtype, ls)) return rc;
   if ((uintptr_t)gcoef & 7) return BINE_ERR_ARG;
   if (!(grad_mul >= 0.0) || std::isinf(grad_mul)) return BINE_ERR_ARG;  // NaN, negative or infinite
   float c[8];
   return bine_adamw_consts(lr, beta1, beta2, eps, weight_decay, step, consts ? consts : c);
 }
 
+int adamw_dyn_args(int n, void *const *p, void *const *m, void *const *v, const void *const *g, void *const *pout,
+                   const size_t *counts, int gdtype, int odtype, const void *state, std::vector<AdamwLaunch> *ls) {
+  if (const int rc = adamw_list_args(n, p, m, v, g, pout, counts, gdtype, odtype, ls)) return rc;
+  return !state || ((uintptr_t)state & 7) ? BINE_ERR_ARG : BINE_SUCCESS;
+}
+
+int step_update_args(const void *state, const void *norm2, const bine_step_hyper *h) {
+  if (!h) return BINE_ERR_ARG;
+  float c[8];
+  if (const int rc = bine_adamw_consts(h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, 1, c)) return rc;
+  if (!(h->max_norm >= 0.0) || !(h->clip_eps >= 0.0)) return BINE_ERR_ARG;  // negative or NaN
+  if (!(h->growth_factor >= 1.0) || std::isinf(h->growth_factor)) return BINE_ERR_ARG;
+  if (!(h->backoff_factor > 0.0 && h->backoff_factor <= 1.0)) return BINE_ERR_ARG;
+  if (h->growth_interval < 1) return BINE_ERR_ARG;
+  if (!(h->min_scale > 0.0 && h->min_scale <= h->max_scale) || std::isinf(h->max_scale)) return BINE_ERR_ARG;
+  if (!state || ((uintptr_t)state & 7) || !norm2 || ((uintptr_t)norm2 & 7)) return BINE_ERR_ARG;
+  return BINE_SUCCESS;
+}
+
 }  // namespace bine
+
+extern "C" int bine_step_state_init(void *host_state, double scale, int64_t step, double beta1, double beta2) {
+  if (!host_state || ((uintptr_t)host_state & 7)) return BINE_ERR_ARG;
+  if (!(scale > 0.0) || std::isinf(scale)) return BINE_ERR_ARG;  // NaN, zero, negative or infinite
+  if (step < 0) return BINE_ERR_ARG;
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return BINE_ERR_ARG;
+  bine::StepState *s = static_cast<bine::StepState *>(host_state);
+  double pw1 = 1.0, pw2 = 1.0;
+  for (int64_t t = 0; t < step; t++) {
+    const double a = pw1 * beta1, b = pw2 * beta2;
+    if (a == pw1 && b == pw2) break;  // zero, or a subnormal the product rounds back to: nothing changes any more
+    pw1 = a, pw2 = b;
+  }
+  *s = bine::StepState{{scale, 0.0, (double)step, pw1, pw2, 0.0, 0.0, 0.0}, {0, 0, 0, 0, 0, 0, 0, 0}};
+  return BINE_SUCCESS;
+}
+
+extern "C" int bine_step_update_host(void *host_state, double norm2, const bine_step_hyper *hyper) {
+  if (const int rc = bine::step_update_args(host_state, &norm2, hyper)) return rc;
+  bine::step_update_rule(static_cast<bine::StepState *>(host_state), norm2, *hyper);
+  return BINE_SUCCESS;
+}
 
 extern "C" int bine_adamw_consts(double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
                                  float out[8]) {
