@@ -167,7 +167,14 @@ const char *bine_status_string(int status);
 const char *bine_last_error(void);
 /* reduce-kernel launch shape (tuning; also env BINE_REDUCE_UNROLL /
  * BINE_REDUCE_MAXBLOCKS / BINE_REDUCE_NT): 16-B vectors in flight per lane
- * (1, 2, 4, 8), grid cap (0 = 2048), non-temporal loads of `in` (fp32 SUM only) */
+ * (1, 2, 4, 8; fp32 SUM only), grid cap in workgroups (0 = the default,
+ * 16384), cache-policy mask (bit 0 / 1: non-temporal loads of `in` / `inout`,
+ * bit 2: non-temporal stores; fp32 SUM only; default 1).  The call governs
+ * only the arithmetic ops (SUM, PROD, MAX, MIN) on the types other than
+ * float16 / bfloat16.  The kernels of those two types and of the logical,
+ * bitwise and MAXLOC / MINLOC ops are compiled separately and take their cap
+ * from BINE_REDUCE_MAXBLOCKS, read once per process at their first call; the
+ * arithmetic ops read BINE_REDUCE_* the same way unless this call came first. */
 int bine_set_reduce_tuning(int unroll, int maxblocks, int nontemporal);
 size_t bine_dtype_size(int dtype);
 /* 1 if MPICH's MPI_Reduce_local accepts (dtype, op): no bitwise op on float /

@@ -304,7 +304,8 @@ def checksum(buf, count: int, dtype=None, stream=None) -> int:
     return out.value
 
 
-def set_reduce_tuning(unroll: int = 4, maxblocks: int = 0, nontemporal: int = 0) -> None:
+def set_reduce_tuning(unroll: int = 4, maxblocks: int = 0, nontemporal: int = 1) -> None:
+    """bine_set_reduce_tuning; with no argument, the library's defaults."""
     lib().bine_set_reduce_tuning(unroll, maxblocks, nontemporal)
 
 

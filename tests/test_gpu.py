@@ -64,13 +64,16 @@ def test_reduce_local_bit_exact(dev, dtype, op):
             a = O.fill(dtype, n, 11 + n)
             b = O.fill(dtype, n, 97 + n)
             ta = to_dev(np.concatenate([np.zeros(shift_a, a.dtype), a]))
-            tb = to_dev(np.concatenate([np.zeros(shift_b, b.dtype), b]))
+            tb = to_dev(np.concatenate([np.zeros(shift_b, b.dtype), b]), pad=64)
             pico_amd.reduce_local(ta.data_ptr() + shift_a * esz, tb.data_ptr() + shift_b * esz, n, dtype, op)
             torch.cuda.synchronize()
             exp = b.copy()
             O.reduce_local(a, exp, dtype, op)
-            got = from_dev(tb, dtype, n, shift_b * esz)
+            raw = tb.cpu().numpy()
+            got = raw[shift_b * esz:(shift_b + n) * esz]
             assert got.tobytes() == exp.tobytes(), (dtype, op, n, shift_a, shift_b)
+            # the elements before inout and the 64 bytes past it stay zero
+            assert not raw[:shift_b * esz].any() and not raw[(shift_b + n) * esz:].any(), (dtype, op, n, shift_b)
 
 
 @pytest.mark.parametrize("dtype", ["float", "double"])
