@@ -3,10 +3,18 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "bine_amd.h"
+
+// what the host planners and the kernels both evaluate (kernels.hip is HIP, every other unit plain C++)
+#if defined(__HIPCC__)
+#define BINE_HOST_DEVICE __attribute__((host)) __attribute__((device))
+#else
+#define BINE_HOST_DEVICE
+#endif
 
 namespace bine {
 
@@ -199,21 +207,47 @@ int launch_reduce_tree_wide_h16(int nl, const void *const *leaf, void *out, size
 // copy_buffer on the device (k_copy); hipMemcpyAsync when src / dst are not
 // co-aligned mod 16 B
 int launch_copy(void *dst, const void *src, size_t bytes, void *stream);
-// segmented copy (bine_copy_segments): the launches of one call, built by the
-// host-only plan_seg_launches (segments.cpp) and issued as k_copy_segs by
-// launch_copy_segments.  A launch carries up to kSegsPerLaunch non-empty
-// segments by value; its grid is the concatenation of their workgroups, one
-// per tile of kCopyTileVecs 16-B vectors (k_copy's tile), at least one per
-// segment; the first workgroup of a segment also copies its head / tail bytes.
+// ---- the segment family (segments.cpp, kernels.hip: TileTable) ------------------
+// Every call that walks a list of buffers is planned on the host (segments.cpp,
+// no HIP) as LaunchTables -- up to N non-empty segments, one workgroup per tile
+// of kCopyTileVecs 16-B vectors, at least one per segment -- and issued by
+// kernels.hip, one launch each (the dispatch: TileTable's comment there).
 constexpr int kSegsPerLaunch = BINE_COPY_SEGS_PER_LAUNCH;
 constexpr uint64_t kCopyTileVecs = 2048;           // kBlock * kCopyU (kernels.hip asserts it)
 constexpr uint64_t kSegMaxWgs = (1u << 24) - 1;    // workgroups of one launch (256 lanes each: below 2^32 lanes)
-struct SegLaunch {
+// A segment's split, the ONE definition planners and kernels share: the bytes
+// before the first 16-B boundary at or after addr (all of them, if the segment
+// ends first) and the whole vectors after those.
+BINE_HOST_DEVICE inline uint64_t seg_head(uint64_t addr, uint64_t bytes) {
+  const uint64_t h = (16 - (addr & 15)) & 15;
+  return h < bytes ? h : bytes;
+}
+BINE_HOST_DEVICE inline uint64_t seg_nvec(uint64_t bytes, uint64_t head) { return (bytes - head) / 16; }
+// one launch as a planner leaves it
+template <int N>
+struct LaunchTable {
   int nseg = 0;
-  int seg[kSegsPerLaunch];             // the caller's segment index per slot
-  uint64_t head[kSegsPerLaunch];       // bytes before the destination's first 16-B boundary
-  uint64_t nvec[kSegsPerLaunch];       // full 16-B vectors after them
-  uint32_t tile0[kSegsPerLaunch + 1];  // first workgroup per slot; [nseg] = the grid
+  int seg[N];                  // the caller's segment (tensor) index per slot
+  uint32_t tile0[N + 1] = {};  // first tile per slot; [nseg] = their number
+};
+// The preamble of every list entry: BINE_ERR_ARG if n is outside [0,
+// BINE_MULTI_MAX] or, with n > 0, `sizes` or one of `lists` is NULL; otherwise
+// the lists' pointers as the addresses the planners take, list i at addr[i * n].
+inline int seg_list_addrs(int n, const size_t *sizes, std::initializer_list<const void *const *> lists,
+                          std::vector<uint64_t> &addr) {
+  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && !sizes)) return BINE_ERR_ARG;
+  addr.clear();
+  for (const void *const *l : lists) {
+    if (n > 0 && !l) return BINE_ERR_ARG;
+    for (int k = 0; k < n; k++) addr.push_back((uint64_t)(uintptr_t)l[k]);
+  }
+  return BINE_SUCCESS;
+}
+// segmented copy (bine_copy_segments): plan_seg_launches' launches, issued as
+// k_copy_segs by launch_copy_segments
+struct SegLaunch : LaunchTable<kSegsPerLaunch> {
+  uint64_t head[kSegsPerLaunch];  // seg_head of the destination
+  uint64_t nvec[kSegsPerLaunch];  // seg_nvec after it
 };
 // BINE_SUCCESS, or BINE_ERR_ARG (n out of range, a NULL array, a zero address
 // with a non-zero size, more than kSegMaxWgs workgroups in one launch)
@@ -230,21 +264,14 @@ int launch_copy_segments(int n, void *const *dsts, const void *const *srcs, cons
 // major: workgroup t is tile t % T (of the tensors' concatenated tiles) of
 // shard t / T, and copies nothing where that shard has fewer tiles.
 constexpr int kShardMaxRanks = 64;  // the library's peer limit (dm::kMaxPeers)
-struct ShardLaunch {
-  int nten = 0;
-  int ten[kSegsPerLaunch];             // the caller's tensor index per slot
-  uint64_t poff[kSegsPerLaunch];       // its shards' offset in a packed block
-  uint32_t tile0[kSegsPerLaunch + 1];  // first tile per slot within one shard's T; [nten] = T
+struct ShardLaunch : LaunchTable<kSegsPerLaunch> {  // seg: tensors; tile0: tiles within one shard's T
+  uint64_t poff[kSegsPerLaunch];                    // the tensor's shards' offset in a packed block
 };
-// the destination of shard j of a tensor (dir 0: packed, dir 1: flat) and the
-// split of its bytes, the expressions k_copy_shards evaluates too
+// the destination of shard j of a tensor (dir 0: packed, dir 1: flat), the
+// expression k_copy_shards evaluates too; its split is seg_head / seg_nvec
 inline uint64_t shard_dst(int dir, uint64_t packed, uint64_t block_bytes, uint64_t poff, uint64_t flat,
                           uint64_t bytes, uint64_t j) {
   return dir ? flat + j * bytes : packed + j * block_bytes + poff;
-}
-inline uint64_t shard_head(uint64_t dst, uint64_t bytes) {
-  const uint64_t h = (16 - (dst & 15)) & 15;
-  return h < bytes ? h : bytes;
 }
 // BINE_SUCCESS, or BINE_ERR_ARG (n, nranks or dir out of range, a NULL array, a
 // zero address with a non-zero size, a tensor that alone exceeds kSegMaxWgs
@@ -255,9 +282,7 @@ int launch_copy_shards(int n, int nranks, int dir, void *packed, void *const *fl
                        void *stream);
 // segmented sum of squares and segmented scale (bine_sumsq_segments /
 // bine_clip_segments): both walk the segmented copy's tile table with
-// destination = source = the buffer, so a tile is up to kCopyTileVecs 16-B
-// ALIGNED vectors of whole elements and a segment's first workgroup also takes
-// the elements before the first and after the last vector.
+// destination = source = the buffer (whole elements per vector).
 // norm_esz: the element size of the four types the two calls take, 0 otherwise.
 size_t norm_esz(int dtype);
 // The checks of a list that need no device, in the header's order (dtype, n, a
@@ -292,11 +317,8 @@ int launch_clip_segments_h16(int n, void *const *bufs, const size_t *counts, int
 constexpr int kAdamwSegsPerLaunch = BINE_ADAMW_SEGS_PER_LAUNCH;
 static_assert(kSegsPerLaunch % kAdamwSegsPerLaunch == 0 && kAdamwSegsPerLaunch <= 64,
               "a SegLaunch splits into whole AdamW launches; AdamwLaunch::elem has one bit per slot");
-struct AdamwLaunch {
-  int nseg = 0;
-  int seg[kAdamwSegsPerLaunch];             // the caller's segment index per slot
-  uint32_t tile0[kAdamwSegsPerLaunch + 1];  // first workgroup per slot; [nseg] = the grid
-  uint64_t elem = 0;                        // bit s: slot s takes the element body
+struct AdamwLaunch : LaunchTable<kAdamwSegsPerLaunch> {
+  uint64_t elem = 0;  // bit s: slot s takes the element body
 };
 // the element size of the three types g and pout take (float, float16,
 // bfloat16), 0 otherwise
@@ -330,11 +352,6 @@ struct StepState {
   float c[8];   // bine_adamw_consts' order
 };
 static_assert(sizeof(StepState) == BINE_STEP_STATE_BYTES && alignof(StepState) == 8, "bine_amd.h's layout");
-#if defined(__HIPCC__)
-#define BINE_HOST_DEVICE __attribute__((host)) __attribute__((device))
-#else
-#define BINE_HOST_DEVICE
-#endif
 BINE_HOST_DEVICE inline void step_update_rule(StepState *s, double n2, const bine_step_hyper &h) {
   double scale = s->d[0];
   if (!(n2 <= 1.7976931348623157e308)) {  // +inf or NaN: some element on some rank was not finite

@@ -532,6 +532,52 @@ int BINE_FN(launch_reduce)(const void *a, const void *b, void *out, size_t count
   });
 }
 
+// ----------------------------------------------------------------------------
+// The segment family's dispatch (k_copy_segs, k_copy_shards, k_sumsq_segs,
+// k_scale_segs, k_adamw_segs), stated once.  A launch takes up to N descriptors
+// BY VALUE in its kernel arguments: no device table to upload, nothing a later
+// call could overwrite while this launch still reads it.  Its grid is the
+// concatenation of the segments' tiles (tile0[k] = slot k's first tile,
+// tile0[nseg] = their number; a tile is kCopyTileVecs 16-B vectors, at least
+// one per segment).  A workgroup finds its slot by a binary search over that
+// prefix (log2 N steps of scalar loads: every value is workgroup-uniform),
+// splits the segment with the planners' own seg_head / seg_nvec into head
+// bytes, 16-B ALIGNED vectors and tail bytes, and runs the kernel's body on its
+// tile; a segment's first workgroup also takes head and tail.  A member is an
+// argument struct {TileTable tab; ...; D s[N]} within 4 KiB, a body, and a
+// planner (segments.cpp) whose LaunchTables fill_segs turns into launches.
+template <int N>
+struct TileTable {
+  uint32_t nseg;
+  uint32_t tile0[N + 1];
+  struct Slot {
+    uint32_t k, wt;
+  };
+  // tile t's slot k and its place wt among the slot's tiles: tile0[k] <= t < tile0[k + 1], nseg >= 1
+  __device__ __forceinline__ Slot find(uint32_t t) const {
+    uint32_t k = 0, hi = nseg;
+    while (hi - k > 1) {
+      const uint32_t mid = (k + hi) >> 1;
+      if (t >= tile0[mid]) k = mid;
+      else hi = mid;
+    }
+    return {k, t - tile0[k]};
+  }
+};
+
+// The host side: tile0 (unused entries = the number of tiles) and slot[s] =
+// desc(s) for the launch's slots, a value-initialised descriptor for the others
+template <int N, typename D, typename F>
+static void fill_slots(const LaunchTable<N> &L, uint32_t (&tile0)[N + 1], D (&slot)[N], F &&desc) {
+  for (int s = 0; s <= N; s++) tile0[s] = L.tile0[s < L.nseg ? s : L.nseg];
+  for (int s = 0; s < N; s++) slot[s] = s < L.nseg ? desc(s) : D{};
+}
+template <typename A, int N, typename F>
+static void fill_segs(A &a, const LaunchTable<N> &L, F &&desc) {
+  a.tab.nseg = (uint32_t)L.nseg;
+  fill_slots(L, a.tab.tile0, a.s, desc);
+}
+
 #if BINE_OPSET == 0
 // ----------------------------------------------------------------------------
 // device copy (copy_buffer): one tile of kBlock * kCopyU 16-B vectors per
@@ -583,15 +629,9 @@ int launch_copy(void *dst, const void *src, size_t bytes, void *stream) {
 
 // ----------------------------------------------------------------------------
 // segmented copy (bine_copy_segments): up to kSegsPerLaunch independent copies
-// in one launch, the descriptors by value in the kernel arguments (no device
-// table to upload, nothing a later call could overwrite while this launch
-// still reads it).  The grid is the concatenation of every segment's tiles, a
-// tile being k_copy's; a workgroup finds its segment by a binary search over
-// the prefix of tile counts (7 steps of scalar loads: every value is
-// workgroup-uniform) and then is k_copy on that segment, its first workgroup
-// copying the head / tail bytes.  Where the source is not co-aligned with the
-// destination mod 16 B the workgroup loads the two 16-B ALIGNED source
-// vectors that hold a destination vector's bytes and shifts them together in
+// in one launch (TileTable's dispatch); a workgroup is k_copy on its segment.
+// Where the source is not co-aligned with the destination mod 16 B the
+// workgroup loads the two 16-B ALIGNED source vectors that hold a destination vector's bytes and shifts them together in
 // registers: no unaligned vector access is issued, the stores stay 16-B
 // aligned, and the extra bytes read lie in 16-B lines that also hold bytes of
 // the segment, so never in another page.
@@ -603,8 +643,7 @@ struct CopySeg {
   uint64_t bytes;
 };
 struct CopySegs {
-  uint32_t nseg;
-  uint32_t tile0[kSegsPerLaunch + 1];
+  TileTable<kSegsPerLaunch> tab;
   CopySeg s[kSegsPerLaunch];
 };
 static_assert(sizeof(CopySegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
@@ -649,7 +688,7 @@ __device__ __forceinline__ void copy_shifted(const u32x4 *va, u32x4 *vd, size_t 
 // head / tail bytes.  A tile past the range's last vector writes nothing.
 __device__ __forceinline__ void copy_range(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, size_t n,
                                            uint32_t wt) {
-  const size_t h = (16 - ((uintptr_t)dst & 15)) & 15, head = h < n ? h : n, nvec = (n - head) / 16;
+  const size_t head = seg_head((uintptr_t)dst, n), nvec = seg_nvec(n, head);
   if (wt == 0) {  // head and tail of this range
     for (size_t i = threadIdx.x; i < head; i += kBlock) dst[i] = src[i];
     for (size_t i = head + nvec * 16 + threadIdx.x; i < n; i += kBlock) dst[i] = src[i];
@@ -687,32 +726,22 @@ __device__ __forceinline__ void copy_range(const uint8_t *__restrict__ src, uint
 }
 
 __global__ __launch_bounds__(kBlock) void k_copy_segs(CopySegs a) {
-  const uint32_t t = blockIdx.x;
-  uint32_t k = 0, hi = a.nseg;  // tile0[k] <= t < tile0[hi]
-  while (hi - k > 1) {
-    const uint32_t mid = (k + hi) >> 1;
-    if (t >= a.tile0[mid]) k = mid;
-    else hi = mid;
-  }
-  copy_range(a.s[k].src, a.s[k].dst, a.s[k].bytes, t - a.tile0[k]);
+  const auto [k, wt] = a.tab.find(blockIdx.x);
+  copy_range(a.s[k].src, a.s[k].dst, a.s[k].bytes, wt);
 }
 
 int launch_copy_segments(int n, void *const *dsts, const void *const *srcs, const size_t *bytes, void *stream) {
-  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!dsts || !srcs || !bytes))) return BINE_ERR_ARG;
-  uint64_t da[BINE_MULTI_MAX], sa[BINE_MULTI_MAX];
-  for (int k = 0; k < n; k++) da[k] = (uint64_t)(uintptr_t)dsts[k], sa[k] = (uint64_t)(uintptr_t)srcs[k];
+  std::vector<uint64_t> addr;
+  if (const int rc = seg_list_addrs(n, bytes, {dsts, srcs}, addr)) return rc;
   std::vector<SegLaunch> ls;
-  if (const int rc = plan_seg_launches(n, da, sa, bytes, ls)) return rc;
+  if (const int rc = plan_seg_launches(n, addr.data(), addr.data() + n, bytes, ls)) return rc;
   hipStream_t st = (hipStream_t)stream;
   for (const SegLaunch &L : ls) {
     CopySegs a;
-    a.nseg = (uint32_t)L.nseg;
-    for (int s = 0; s < L.nseg; s++) {
-      a.tile0[s] = L.tile0[s];
-      a.s[s] = {(const uint8_t *)srcs[L.seg[s]], (uint8_t *)dsts[L.seg[s]], (uint64_t)bytes[L.seg[s]]};
-    }
-    for (int s = L.nseg; s <= kSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nseg];
-    for (int s = L.nseg; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, nullptr, 0};
+    fill_segs(a, L, [&](int s) {
+      const int k = L.seg[s];
+      return CopySeg{(const uint8_t *)srcs[k], (uint8_t *)dsts[k], (uint64_t)bytes[k]};
+    });
     hipLaunchKernelGGL(k_copy_segs, dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
     if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
   }
@@ -723,13 +752,13 @@ int launch_copy_segments(int n, void *const *dsts, const void *const *srcs, cons
 // sharded copy (bine_copy_shards): all P shards of up to kSegsPerLaunch tensors
 // in one launch, between the flat layout (shard j of tensor k at flat[k] +
 // j * bytes[k]) and the packed one (packed + j * block + poff[k]) -- the
-// strided layout change of a sharded bucket, one descriptor per TENSOR, by
-// value as k_copy_segs' are.  With T = the tensors' tiles per shard summed, the
-// grid is P x T workgroups, shard major: one division of workgroup-uniform
-// values gives a workgroup its shard (t / T) and its place among one shard's
-// tiles (t % T), k_copy_segs' binary search over the prefix of tiles per shard
-// gives its tensor and its tile, and then it is k_copy_segs on that shard's
-// (source, destination, bytes): copy_range.  Neighbouring workgroups so copy
+// strided layout change of a sharded bucket, one descriptor per TENSOR
+// (TileTable's dispatch over the tiles of ONE shard).  With T = the tensors'
+// tiles per shard summed, the grid is P x T workgroups, shard major: one
+// division of workgroup-uniform values gives a workgroup its shard (t / T) and
+// its place among one shard's tiles (t % T), the table's search its tensor and
+// its tile, and then it is k_copy_segs on that shard's (source, destination,
+// bytes): copy_range.  Neighbouring workgroups so copy
 // neighbouring tiles, as they do in k_copy_segs (tile major and shard minor --
 // P streams 4 MiB apart -- measured 6 % slower on 8 x 8 x 4 MiB).  The
 // destination's phase may differ from shard to shard, so a tensor's tiles per
@@ -741,8 +770,8 @@ struct CopyShard {
   uint64_t bytes;  // of one shard
 };
 struct CopyShards {
-  uint32_t nten, nranks, dir;  // dir 0: flat -> packed, 1: packed -> flat
-  uint32_t tile0[kSegsPerLaunch + 1];
+  TileTable<kSegsPerLaunch> tab;  // of one shard's tiles: tile0[nseg] = T
+  uint32_t nranks, dir;           // dir 0: flat -> packed, 1: packed -> flat
   uint8_t *packed;
   uint64_t block;  // bytes of a packed block: the sum of every tensor's shard bytes
   CopyShard s[kSegsPerLaunch];
@@ -750,14 +779,8 @@ struct CopyShards {
 static_assert(sizeof(CopyShards) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
 
 __global__ __launch_bounds__(kBlock) void k_copy_shards(CopyShards a) {
-  const uint32_t T = a.tile0[a.nten], j = blockIdx.x / T, t = blockIdx.x - j * T;
-  uint32_t k = 0, hi = a.nten;  // tile0[k] <= t < tile0[hi]
-  while (hi - k > 1) {
-    const uint32_t mid = (k + hi) >> 1;
-    if (t >= a.tile0[mid]) k = mid;
-    else hi = mid;
-  }
-  const uint32_t wt = t - a.tile0[k];
+  const uint32_t T = a.tab.tile0[a.tab.nseg], j = blockIdx.x / T;
+  const auto [k, wt] = a.tab.find(blockIdx.x - j * T);
   const size_t n = a.s[k].bytes;
   uint8_t *fl = a.s[k].flat + (size_t)j * n;
   uint8_t *pk = a.packed + (size_t)j * a.block + a.s[k].poff;
@@ -766,25 +789,20 @@ __global__ __launch_bounds__(kBlock) void k_copy_shards(CopyShards a) {
 
 int launch_copy_shards(int n, int nranks, int dir, void *packed, void *const *flat, const size_t *bytes,
                        void *stream) {
-  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!flat || !bytes))) return BINE_ERR_ARG;
-  uint64_t fa[BINE_MULTI_MAX];
-  for (int k = 0; k < n; k++) fa[k] = (uint64_t)(uintptr_t)flat[k];
+  std::vector<uint64_t> addr;
+  if (const int rc = seg_list_addrs(n, bytes, {flat}, addr)) return rc;
   std::vector<ShardLaunch> ls;
   uint64_t block = 0;
-  if (const int rc = plan_shard_launches(n, nranks, dir, (uint64_t)(uintptr_t)packed, fa, bytes, ls, &block))
+  if (const int rc =
+          plan_shard_launches(n, nranks, dir, (uint64_t)(uintptr_t)packed, addr.data(), bytes, ls, &block))
     return rc;
   hipStream_t st = (hipStream_t)stream;
   for (const ShardLaunch &L : ls) {
     CopyShards a;
-    a.nten = (uint32_t)L.nten, a.nranks = (uint32_t)nranks, a.dir = (uint32_t)dir;
+    a.nranks = (uint32_t)nranks, a.dir = (uint32_t)dir;
     a.packed = (uint8_t *)packed, a.block = block;
-    for (int s = 0; s < L.nten; s++) {
-      a.tile0[s] = L.tile0[s];
-      a.s[s] = {(uint8_t *)flat[L.ten[s]], L.poff[s], (uint64_t)bytes[L.ten[s]]};
-    }
-    for (int s = L.nten; s <= kSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nten];
-    for (int s = L.nten; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, 0, 0};
-    hipLaunchKernelGGL(k_copy_shards, dim3(L.tile0[L.nten] * (uint32_t)nranks), dim3(kBlock), 0, st, a);
+    fill_segs(a, L, [&](int s) { return CopyShard{(uint8_t *)flat[L.seg[s]], L.poff[s], (uint64_t)bytes[L.seg[s]]}; });
+    hipLaunchKernelGGL(k_copy_shards, dim3(L.tile0[L.nseg] * (uint32_t)nranks), dim3(kBlock), 0, st, a);
     if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
   }
   return BINE_SUCCESS;
@@ -1327,29 +1345,16 @@ int BINE_FN(launch_scale)(const void *in, void *out, size_t count, int dtype, do
 // ----------------------------------------------------------------------------
 // segmented sum of squares and segmented scale (bine_sumsq_segments /
 // bine_clip_segments: the global gradient norm and the clipping of a bucket).
-// Both take k_copy_segs' dispatch -- up to kSegsPerLaunch descriptors by value,
-// the grid the concatenation of the segments' tiles, a binary search over the
-// tile prefix -- over the table plan_seg_launches builds with destination =
-// source = the buffer (plan_norm_launches): a tile is kBlock * kScaleU 16-B
-// aligned vectors of whole elements, and a segment's first workgroup also
-// takes the elements before the first and after the last vector.
+// Both take TileTable's dispatch over the table plan_seg_launches builds with
+// destination = source = the buffer (plan_norm_launches): a tile is kBlock *
+// kScaleU 16-B aligned vectors of whole elements, and a segment's first
+// workgroup also takes the elements before the first and after the last vector.
 static_assert(kCopyTileVecs == (uint64_t)kBlock * kScaleU, "the planner's tile is k_scale's");
 
 struct NormSeg {
   uint8_t *p;
   uint64_t bytes;
 };
-
-// tile0[k] <= t < tile0[k + 1], nseg >= 1 (workgroup-uniform: scalar loads)
-__device__ __forceinline__ uint32_t seg_of_tile(const uint32_t *tile0, uint32_t nseg, uint32_t t) {
-  uint32_t k = 0, hi = nseg;
-  while (hi - k > 1) {
-    const uint32_t mid = (k + hi) >> 1;
-    if (t >= tile0[mid]) k = mid;
-    else hi = mid;
-  }
-  return k;
-}
 
 // The workgroup's sum of one double per lane, in an order fixed by the lane
 // numbers alone: the 64 lanes of a wave by a butterfly of __shfl_xor (both
@@ -1390,8 +1395,7 @@ __device__ __forceinline__ double sumsq16(u32x4 v) {
 // order decided by arrival: the bits depend on the data, the counts, the type
 // and the buffers' addresses mod 16 B alone.
 struct SumsqSegs {
-  uint32_t nseg;
-  uint32_t tile0[kSegsPerLaunch + 1];
+  TileTable<kSegsPerLaunch> tab;
   double *scratch;  // this launch's first workgroup's double
   NormSeg s[kSegsPerLaunch];
 };
@@ -1400,10 +1404,11 @@ static_assert(sizeof(SumsqSegs) <= 4096, "by-value kernel arguments: within HIP'
 template <typename T, bool NT>
 __global__ __launch_bounds__(kBlock) void k_sumsq_segs(SumsqSegs a) {
   __shared__ double part[kBlock / 64];
-  const uint32_t t = blockIdx.x, k = seg_of_tile(a.tile0, a.nseg, t), wt = t - a.tile0[k];
+  const uint32_t t = blockIdx.x;
+  const auto [k, wt] = a.tab.find(t);
   const uint8_t *p = a.s[k].p;
   const size_t n = a.s[k].bytes;
-  const size_t h = (16 - ((uintptr_t)p & 15)) & 15, head = h < n ? h : n, nvec = (n - head) / 16;
+  const size_t head = seg_head((uintptr_t)p, n), nvec = seg_nvec(n, head);
   double acc = 0.0;
   if (wt == 0) {  // head and tail elements of this segment
     const T *e = reinterpret_cast<const T *>(p);
@@ -1442,14 +1447,10 @@ int BINE_FN(launch_sumsq_tiles)(const std::vector<SegLaunch> &ls, const void *co
       uint64_t t0 = 0;
       for (const SegLaunch &L : ls) {
         SumsqSegs a;
-        a.nseg = (uint32_t)L.nseg;
         a.scratch = scratch + t0;
-        for (int s = 0; s < L.nseg; s++) {
-          a.tile0[s] = L.tile0[s];
-          a.s[s] = {(uint8_t *)const_cast<void *>(bufs[L.seg[s]]), (uint64_t)(counts[L.seg[s]] * sizeof(T))};
-        }
-        for (int s = L.nseg; s <= kSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nseg];
-        for (int s = L.nseg; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, 0};
+        fill_segs(a, L, [&](int s) {
+          return NormSeg{(uint8_t *)const_cast<void *>(bufs[L.seg[s]]), (uint64_t)(counts[L.seg[s]] * sizeof(T))};
+        });
         if (nt) hipLaunchKernelGGL((k_sumsq_segs<T, true>), dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
         else hipLaunchKernelGGL((k_sumsq_segs<T, false>), dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
         if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
@@ -1513,12 +1514,11 @@ static bool sumsq_nt() {
 int launch_sumsq_segments(int n, const void *const *bufs, const size_t *counts, int dtype, double *out,
                           double *scratch, size_t scratch_doubles, void *stream) {
   if (!norm_esz(dtype)) return BINE_ERR_ARG;
-  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!bufs || !counts))) return BINE_ERR_ARG;
-  uint64_t addr[BINE_MULTI_MAX];
-  for (int k = 0; k < n; k++) addr[k] = (uint64_t)(uintptr_t)bufs[k];
+  std::vector<uint64_t> addr;
+  if (const int rc = seg_list_addrs(n, counts, {bufs}, addr)) return rc;
   std::vector<SegLaunch> ls;
   uint64_t tiles = 0;
-  if (const int rc = plan_norm_launches(n, addr, counts, dtype, ls, &tiles)) return rc;
+  if (const int rc = plan_norm_launches(n, addr.data(), counts, dtype, ls, &tiles)) return rc;
   if (!out || ((uintptr_t)out & 7)) return BINE_ERR_ARG;
   if (scratch_doubles < tiles || (tiles && (!scratch || ((uintptr_t)scratch & 7)))) return BINE_ERR_ARG;
   if (const int rc = launch_sumsq_tiles(ls, bufs, counts, dtype, scratch, sumsq_nt(), stream)) return rc;
@@ -1526,8 +1526,7 @@ int launch_sumsq_segments(int n, const void *const *bufs, const size_t *counts, 
   uint64_t t0 = 0;
   for (const SegLaunch &L : ls) {
     SumsqFold f;
-    for (int s = 0; s <= kSegsPerLaunch; s++) f.tile0[s] = L.tile0[s < L.nseg ? s : L.nseg];
-    for (int s = 0; s < kSegsPerLaunch; s++) f.seg[s] = (uint16_t)(s < L.nseg ? L.seg[s] : 0);
+    fill_slots(L, f.tile0, f.seg, [&](int s) { return (uint16_t)L.seg[s]; });
     f.scratch = scratch + t0;
     f.out = out;
     hipLaunchKernelGGL(k_sumsq_fold, dim3((unsigned)L.nseg), dim3(kBlock), 0, st, f);
@@ -1553,8 +1552,7 @@ int launch_sumsq_segments(int n, const void *const *bufs, const size_t *counts, 
 // it to *coef_out.  c == 1.0: nothing is stored.  A full tile's loads are
 // issued before the coefficient's arithmetic, which so overlaps them.
 struct ScaleSegs {
-  uint32_t nseg;  // 0: the launch only stores the coefficient
-  uint32_t tile0[kSegsPerLaunch + 1];
+  TileTable<kSegsPerLaunch> tab;  // nseg 0: the launch only stores the coefficient
   const double *norm2;
   double *coef_out;  // NULL: not stored
   double max_norm, eps;
@@ -1571,11 +1569,11 @@ template <typename T>
 __global__ __launch_bounds__(kBlock) void k_scale_segs(ScaleSegs a) {
   constexpr size_t V = 16 / sizeof(T);
   if (blockIdx.x == 0 && threadIdx.x == 0 && a.coef_out) *a.coef_out = clip_coef(a);
-  if (a.nseg == 0) return;
-  const uint32_t t = blockIdx.x, k = seg_of_tile(a.tile0, a.nseg, t), wt = t - a.tile0[k];
+  if (a.tab.nseg == 0) return;
+  const auto [k, wt] = a.tab.find(blockIdx.x);
   uint8_t *p = a.s[k].p;
   const size_t n = a.s[k].bytes;
-  const size_t h = (16 - ((uintptr_t)p & 15)) & 15, head = h < n ? h : n, nvec = (n - head) / 16;
+  const size_t head = seg_head((uintptr_t)p, n), nvec = seg_nvec(n, head);
   u32x4 *vd = reinterpret_cast<u32x4 *>(p + head);
   const size_t base = (size_t)wt * kBlock * kScaleU + threadIdx.x;
   const bool full = base + (kScaleU - 1) * (size_t)kBlock < nvec;
@@ -1609,15 +1607,14 @@ __global__ __launch_bounds__(kBlock) void k_scale_segs(ScaleSegs a) {
 int BINE_FN(launch_clip_segments)(int n, void *const *bufs, const size_t *counts, int dtype, const double *norm2,
                                   double max_norm, double eps, double *coef_out, void *stream) {
   if (!norm_esz(dtype)) return BINE_ERR_ARG;
-  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!bufs || !counts))) return BINE_ERR_ARG;
 #if BINE_OPSET == 0
-  if (h16_dtype(dtype))
+  if (h16_dtype(dtype))  // the twin runs every check below
     return launch_clip_segments_h16(n, bufs, counts, dtype, norm2, max_norm, eps, coef_out, stream);
 #endif
-  uint64_t addr[BINE_MULTI_MAX];
-  for (int k = 0; k < n; k++) addr[k] = (uint64_t)(uintptr_t)bufs[k];
+  std::vector<uint64_t> addr;
+  if (const int rc = seg_list_addrs(n, counts, {bufs}, addr)) return rc;
   std::vector<SegLaunch> ls;
-  if (const int rc = plan_norm_launches(n, addr, counts, dtype, ls, nullptr)) return rc;
+  if (const int rc = plan_norm_launches(n, addr.data(), counts, dtype, ls, nullptr)) return rc;
   if (!norm2 || ((uintptr_t)norm2 & 7) || ((uintptr_t)coef_out & 7)) return BINE_ERR_ARG;
   if (!(max_norm >= 0.0) || !(eps >= 0.0)) return BINE_ERR_ARG;  // negative or NaN
   hipStream_t st = (hipStream_t)stream;
@@ -1626,22 +1623,19 @@ int BINE_FN(launch_clip_segments)(int n, void *const *bufs, const size_t *counts
     if constexpr (kScaleT<T>) {
       ScaleSegs a;
       a.norm2 = norm2, a.coef_out = coef_out, a.max_norm = max_norm, a.eps = eps;
-      if (ls.empty()) {  // nothing to scale: the coefficient alone
+      auto fill = [&](const SegLaunch &L) {
+        fill_segs(a, L, [&](int s) {
+          return NormSeg{(uint8_t *)bufs[L.seg[s]], (uint64_t)(counts[L.seg[s]] * sizeof(T))};
+        });
+      };
+      if (ls.empty()) {  // nothing to scale: the coefficient alone, from a launch without segments
         if (!coef_out) return BINE_SUCCESS;
-        a.nseg = 0;
-        for (int s = 0; s <= kSegsPerLaunch; s++) a.tile0[s] = 0;
-        for (int s = 0; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, 0};
+        fill(SegLaunch{});
         hipLaunchKernelGGL((k_scale_segs<T>), dim3(1), dim3(kBlock), 0, st, a);
         return status(hipGetLastError());
       }
       for (const SegLaunch &L : ls) {
-        a.nseg = (uint32_t)L.nseg;
-        for (int s = 0; s < L.nseg; s++) {
-          a.tile0[s] = L.tile0[s];
-          a.s[s] = {(uint8_t *)bufs[L.seg[s]], (uint64_t)(counts[L.seg[s]] * sizeof(T))};
-        }
-        for (int s = L.nseg; s <= kSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nseg];
-        for (int s = L.nseg; s < kSegsPerLaunch; s++) a.s[s] = {nullptr, 0};
+        fill(L);
         hipLaunchKernelGGL((k_scale_segs<T>), dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
         if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
         a.coef_out = nullptr;  // stored once, by the first launch
@@ -2028,12 +2022,10 @@ int launch_narrow_h16(const void *in32, void *out16, size_t count, int dtype, vo
 // k_adamw_segs: one AdamW step over a list of shards (bine_adamw_segments,
 // bine_amd.h).  p, m, v are binary32 and updated in place, g (G: float,
 // float16, bfloat16) is read only, pout (O, optional) receives the new
-// parameter narrowed.  k_scale_segs' dispatch -- descriptors by value, the grid
-// the concatenation of the segments' tiles, seg_of_tile's search -- over
-// plan_norm_launches' table of p, cut at kAdamwSegsPerLaunch descriptors
-// (plan_adamw_launches): a tile is kBlock * kScaleU 16-B aligned vectors of p,
-// and a segment's first workgroup also takes the elements before the first
-// and after the last vector.
+// parameter narrowed.  TileTable's dispatch over plan_norm_launches' table of
+// p, cut at kAdamwSegsPerLaunch descriptors (plan_adamw_launches): a tile is
+// kBlock * kScaleU 16-B aligned vectors of p, and a segment's first workgroup
+// also takes the elements before the first and after the last vector.
 //
 // Every line of adamw1 is one correctly rounded binary32 operation
 // (-ffp-contract=off: no FMA; IEEE division and square root; subnormals kept).
@@ -2053,8 +2045,7 @@ struct AdamwSeg {
   uint64_t n;  // elements
 };
 struct AdamwSegs {
-  uint32_t nseg;
-  uint32_t tile0[kAdamwSegsPerLaunch + 1];
+  TileTable<kAdamwSegsPerLaunch> tab;
   uint64_t elem;        // bit s: slot s takes the element body
   const double *gcoef;  // NULL: 1.0
   double grad_mul;
@@ -2134,12 +2125,13 @@ template <typename G, typename O, bool PO, bool DYN = false>
 __global__ __launch_bounds__(kBlock) void k_adamw_segs(AdamwSegs a) {
   using GV = vec4_of<G>;
   using OV = vec4_of<O>;
-  const uint32_t t = blockIdx.x, k = seg_of_tile(a.tile0, a.nseg, t), wt = t - a.tile0[k];
+  const auto [k, wt] = a.tab.find(blockIdx.x);
   float *p = a.s[k].p, *m = a.s[k].m, *v = a.s[k].v;
   const G *g = static_cast<const G *>(a.s[k].g);
   [[maybe_unused]] O *po = static_cast<O *>(a.s[k].pout);
   const size_t n = a.s[k].n;
-  const size_t h = ((16 - ((uintptr_t)p & 15)) & 15) / 4, he = h < n ? h : n, nvec = (n - he) / 4;
+  // the split in elements: p is 4-B aligned, so the head is whole elements and a vector is four
+  const size_t he = seg_head((uintptr_t)p, 4 * n) / 4, nvec = (n - he) / 4;
   const bool elem = (a.elem >> k) & 1;
   u32x4 *vp = reinterpret_cast<u32x4 *>(p + he), *vm = reinterpret_cast<u32x4 *>(m + he);
   u32x4 *vv = reinterpret_cast<u32x4 *>(v + he);
@@ -2227,15 +2219,12 @@ static int adamw_issue(AdamwSegs &a, const std::vector<AdamwLaunch> &ls, void *c
     return with_adamw_dtype(odtype, [&](auto otag) -> int {
       using O = typename decltype(otag)::type;
       for (const AdamwLaunch &L : ls) {
-        a.nseg = (uint32_t)L.nseg;
         a.elem = L.elem;
-        for (int s = 0; s < L.nseg; s++) {
+        fill_segs(a, L, [&](int s) {
           const int k = L.seg[s];
-          a.tile0[s] = L.tile0[s];
-          a.s[s] = {(float *)p[k], (float *)m[k], (float *)v[k], g[k], pout ? pout[k] : nullptr, (uint64_t)counts[k]};
-        }
-        for (int s = L.nseg; s <= kAdamwSegsPerLaunch; s++) a.tile0[s] = L.tile0[L.nseg];
-        for (int s = L.nseg; s < kAdamwSegsPerLaunch; s++) a.s[s] = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+          return AdamwSeg{(float *)p[k], (float *)m[k], (float *)v[k], g[k], pout ? pout[k] : nullptr,
+                          (uint64_t)counts[k]};
+        });
         const dim3 grid(L.tile0[L.nseg]), blk(kBlock);
         // without pout one instantiation per G serves every odtype
         if (pout) hipLaunchKernelGGL((k_adamw_segs<G, O, true, DYN>), grid, blk, 0, st, a);

@@ -1,20 +1,19 @@
-// segments.cpp -- the tile tables of the segmented copy (bine_copy_segments)
-// and of the sharded copy (bine_copy_shards).
+// segments.cpp -- the planners of the segment family: the LaunchTables
+// (bine_internal.h) that kernels.hip issues, one kernel launch each.
 //
 // Host only, no HIP: plain C++ over addresses and sizes, so the CPU suite can
-// check the cover (bine_plan_segments) and a stand-alone program can run it
-// under the host sanitizers (tools/segments_check.cpp).  launch_copy_segments
-// (kernels.hip) issues exactly the launches plan_seg_launches returns, and
-// k_copy_segs derives a segment's head and vector count from the same two
-// expressions (seg_head / seg_nvec) over the same descriptor.  The sharded
-// copy is built the same way: plan_shard_launches / bine_plan_shards are what
-// launch_copy_shards issues as k_copy_shards (tools/shards_check.cpp).  The
-// segmented sum of squares and the segmented scale walk plan_seg_launches'
-// table over the buffers themselves: plan_norm_launches / bine_plan_sumsq
-// (tools/sumsq_check.cpp).  The fused AdamW step walks plan_norm_launches' table
-// over p and cuts it at kAdamwSegsPerLaunch descriptors: plan_adamw_launches /
-// bine_plan_adamw, with the step's constants (bine_adamw_consts) beside them
-// (tools/adamw_check.cpp).  Dynamic loss scaling keeps its host half here too:
+// check the cover (bine_plan_*) and stand-alone programs can run the planners
+// under the host sanitizers (tools/*_check.cpp).  A kernel derives a segment's
+// head and vector count by calling the functions the planners call (seg_head /
+// seg_nvec, bine_internal.h) on the same descriptor.
+//   plan_seg_launches / bine_plan_segments   k_copy_segs    (tools/segments_check.cpp)
+//   plan_shard_launches / bine_plan_shards   k_copy_shards  (tools/shards_check.cpp)
+//   plan_norm_launches / bine_plan_sumsq     k_sumsq_segs, k_scale_segs: plan_seg_launches'
+//                                            table over the buffers themselves (tools/sumsq_check.cpp)
+//   plan_adamw_launches / bine_plan_adamw    k_adamw_segs: plan_norm_launches' table over p, cut at
+//                                            kAdamwSegsPerLaunch descriptors, with the step's constants
+//                                            (bine_adamw_consts) beside them (tools/adamw_check.cpp)
+// Dynamic loss scaling keeps its host half here too:
 // bine_step_state_init, the refusals (step_update_args, adamw_dyn_args) and
 // bine_step_update_host, the host compilation of the statement k_step_update
 // runs (step_update_rule, bine_internal.h; tools/step_check.cpp).
@@ -25,12 +24,6 @@
 
 namespace bine {
 
-static uint64_t seg_head(uint64_t dst, uint64_t bytes) {
-  const uint64_t h = (16 - (dst & 15)) & 15;
-  return h < bytes ? h : bytes;
-}
-static uint64_t seg_nvec(uint64_t bytes, uint64_t head) { return (bytes - head) / 16; }
-
 int plan_seg_launches(int n, const uint64_t *dst_addr, const uint64_t *src_addr, const size_t *bytes,
                       std::vector<SegLaunch> &out) {
   out.clear();
@@ -39,10 +32,7 @@ int plan_seg_launches(int n, const uint64_t *dst_addr, const uint64_t *src_addr,
   for (int k = 0; k < n; k++) {
     if (bytes[k] == 0) continue;
     if (!dst_addr[k] || !src_addr[k]) return BINE_ERR_ARG;
-    if (out.empty() || out.back().nseg == kSegsPerLaunch) {
-      out.emplace_back();
-      out.back().tile0[0] = 0;
-    }
+    if (out.empty() || out.back().nseg == kSegsPerLaunch) out.emplace_back();
     SegLaunch &L = out.back();
     const int s = L.nseg++;
     L.seg[s] = k;
@@ -63,7 +53,7 @@ static uint64_t shard_tiles(int nranks, int dir, uint64_t packed, uint64_t block
                             uint64_t bytes) {
   uint64_t tps = 1;
   for (int j = 0; j < nranks && j < 16; j++) {
-    const uint64_t nvec = seg_nvec(bytes, shard_head(shard_dst(dir, packed, block, poff, flat, bytes, j), bytes));
+    const uint64_t nvec = seg_nvec(bytes, seg_head(shard_dst(dir, packed, block, poff, flat, bytes, j), bytes));
     tps = std::max(tps, (nvec + kCopyTileVecs - 1) / kCopyTileVecs);
   }
   return tps;
@@ -92,14 +82,12 @@ int plan_shard_launches(int n, int nranks, int dir, uint64_t packed_addr, const 
     // tile0 counts tiles per shard; the launch's grid is nranks times its total
     const uint64_t tps = shard_tiles(nranks, dir, packed_addr, block, poff, flat_addr[k], bytes[k]);
     if (tps * nranks > kSegMaxWgs) return BINE_ERR_ARG;
-    if (out.empty() || out.back().nten == kSegsPerLaunch ||
-        (out.back().tile0[out.back().nten] + tps) * nranks > kSegMaxWgs) {
+    if (out.empty() || out.back().nseg == kSegsPerLaunch ||
+        (out.back().tile0[out.back().nseg] + tps) * nranks > kSegMaxWgs)
       out.emplace_back();
-      out.back().tile0[0] = 0;
-    }
     ShardLaunch &L = out.back();
-    const int s = L.nten++;
-    L.ten[s] = k;
+    const int s = L.nseg++;
+    L.seg[s] = k;
     L.poff[s] = poff;
     L.tile0[s + 1] = (uint32_t)(L.tile0[s] + tps);
     poff += bytes[k];
@@ -171,9 +159,10 @@ int plan_adamw_launches(int n, const uint64_t *p, const uint64_t *m, const uint6
         const int k = L.seg[s0 + s];
         A.seg[s] = k;
         A.tile0[s] = L.tile0[s0 + s] - L.tile0[s0];
-        // h: the elements before p's first 16-B boundary; the vector body needs
-        // every other operand on a boundary of its own 4-element vector there
-        const uint64_t h = ((16 - (p[k] & 15)) & 15) / 4;
+        // h: the elements before p's first 16-B boundary (seg_head of a span that
+        // reaches it: the flag is the addresses', whatever the count); the vector body
+        // needs every other operand on a boundary of its own 4-element vector there
+        const uint64_t h = seg_head(p[k], 16) / 4;
         const bool vec = (m[k] + 4 * h) % 16 == 0 && (v[k] + 4 * h) % 16 == 0 && (g[k] + gsz * h) % (4 * gsz) == 0 &&
                          (!pout || (pout[k] + osz * h) % (4 * osz) == 0);
         if (!vec) A.elem |= (uint64_t)1 << s;
@@ -188,15 +177,13 @@ static int adamw_list_args(int n, void *const *p, void *const *m, void *const *v
                            void *const *pout, const size_t *counts, int gdtype, int odtype,
                            std::vector<AdamwLaunch> *ls) {
   if (!adamw_esz(gdtype) || !adamw_esz(odtype)) return BINE_ERR_ARG;
-  if (n < 0 || n > BINE_MULTI_MAX || (n > 0 && (!p || !m || !v || !g || !counts))) return BINE_ERR_ARG;
-  std::vector<uint64_t> a((size_t)5 * (n > 0 ? n : 1));
-  uint64_t *pa = a.data(), *ma = pa + n, *va = ma + n, *ga = va + n, *oa = ga + n;
-  for (int k = 0; k < n; k++) {
-    pa[k] = (uint64_t)(uintptr_t)p[k], ma[k] = (uint64_t)(uintptr_t)m[k], va[k] = (uint64_t)(uintptr_t)v[k];
-    ga[k] = (uint64_t)(uintptr_t)g[k], oa[k] = pout ? (uint64_t)(uintptr_t)pout[k] : 0;
-  }
+  std::vector<uint64_t> a, o;  // p, m, v, g; the optional pout
+  if (const int rc = seg_list_addrs(n, counts, {p, m, v, g}, a)) return rc;
+  if (pout) seg_list_addrs(n, counts, {pout}, o);
   std::vector<AdamwLaunch> local;
-  return plan_adamw_launches(n, pa, ma, va, ga, pout ? oa : nullptr, counts, gdtype, odtype, ls ? *ls : local);
+  const uint64_t *pa = a.data();
+  return plan_adamw_launches(n, pa, pa + n, pa + 2 * n, pa + 3 * n, pout ? o.data() : nullptr, counts, gdtype, odtype,
+                             ls ? *ls : local);
 }
 
 int adamw_args(int n, void *const *p, void *const *m, void *const *v, const void *const *g, void *const *pout,
@@ -313,11 +300,11 @@ extern "C" int64_t bine_plan_shards(int n, int nranks, int dir, uint64_t packed_
   };
   for (size_t l = 0; l < ls.size(); l++) {
     const bine::ShardLaunch &L = ls[l];
-    for (int s = 0; s < L.nten; s++) {
-      const uint64_t k = (uint64_t)L.ten[s], b = shard_bytes[k];
+    for (int s = 0; s < L.nseg; s++) {
+      const uint64_t k = (uint64_t)L.seg[s], b = shard_bytes[k];
       for (uint64_t j = 0; j < (uint64_t)nranks; j++) {
         const uint64_t head =
-            bine::shard_head(bine::shard_dst(dir, packed_addr, block, L.poff[s], flat_addr[k], b, j), b);
+            bine::seg_head(bine::shard_dst(dir, packed_addr, block, L.poff[s], flat_addr[k], b, j), b);
         const uint64_t nvec = bine::seg_nvec(b, head), tail = b - head - 16 * nvec;
         if (head) put(l, k, j, 0, head, 1);
         for (uint64_t v = 0; v < nvec; v += bine::kCopyTileVecs)
