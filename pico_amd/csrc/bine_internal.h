@@ -3,6 +3,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <initializer_list>
 #include <string>
 #include <vector>
@@ -207,6 +208,30 @@ int launch_reduce_tree_wide_h16(int nl, const void *const *leaf, void *out, size
 // copy_buffer on the device (k_copy); hipMemcpyAsync when src / dst are not
 // co-aligned mod 16 B
 int launch_copy(void *dst, const void *src, size_t bytes, void *stream);
+// k_copy's cache policy: copies of at least min_bytes load their first
+// keep_bytes with the default policy (they may stay in the Infinity Cache for
+// the next copy of the same source), everything else non-temporally.
+struct CopyKeep {
+  uint64_t keep_bytes, min_bytes;
+};
+// the policy with BINE_COPY_KEEP_MIB = env (NULL: unset): a number of MiB >= 0,
+// fractions allowed, replaces def_keep and applies to copies of every size
+// (0: every load non-temporal); unset or not such a number: the defaults
+inline CopyKeep copy_keep_policy(const char *env, uint64_t def_keep, uint64_t def_min) {
+  if (!env || !*env) return {def_keep, def_min};
+  char *end = nullptr;
+  const double mib = strtod(env, &end);
+  if (end == env || *end || !(mib >= 0.0)) return {def_keep, def_min};
+  const double cap = 1099511627776.0;  // 2^40 MiB = 2^60 bytes: the conversion below stays in range
+  return {(uint64_t)((mib < cap ? mib : cap) * 1048576.0), 0};
+}
+// k_copy's keep_vecs for a copy of `bytes` bytes with nvec whole vectors: never
+// above nvec, 0 below the policy's size threshold
+inline uint64_t copy_keep_vecs(uint64_t bytes, uint64_t nvec, const CopyKeep &p) {
+  if (bytes < p.min_bytes) return 0;
+  const uint64_t k = p.keep_bytes / 16;
+  return k < nvec ? k : nvec;
+}
 // ---- the segment family (segments.cpp, kernels.hip: TileTable) ------------------
 // Every call that walks a list of buffers is planned on the host (segments.cpp,
 // no HIP) as LaunchTables -- up to N non-empty segments, one workgroup per tile

@@ -15,7 +15,10 @@
 //    libbine_allreduce.c:849-852 -- the whole P = 1 allreduce).  16-B vectors,
 //    8 per lane in flight, non-temporal loads AND stores: 83 us for 256 MiB
 //    (6.44 TB/s of read + write) vs 98.6 us for hipMemcpyAsync D2D
-//    (tools/copy_variants.hip, profiles/r2_copy_variants.txt).
+//    (tools/copy_variants.hip, profiles/r2_copy_variants.txt).  Copies of
+//    128 MiB and more load their first 192 MiB with the default policy, so a
+//    source copied again is partly found in the Infinity Cache: 79.4 us for
+//    the same 256 MiB back to back (profiles/copy_mall_split.txt).
 //  * k_fill_pico: pico_core's rand_r() input distributions
 //    (pico_core_utils.c:902-923) generated in parallel by LCG jump-ahead,
 //    bit-identical to the sequential host generator.
@@ -584,23 +587,60 @@ static void fill_segs(A &a, const LaunchTable<N> &L, F &&desc) {
 // workgroup, loads issued before stores, both non-temporal (the copied bytes
 // are not re-read by this launch).  Bytes before the first 16-B boundary of
 // `dst` and after the last full vector go byte-wise through workgroup 0.
+//
+// Cache policy: the tiles whose first vector lies below `keep_vecs` load with
+// the default policy, so a large copy's first bytes may stay in the 256 MiB
+// Infinity Cache for the next copy of the same source; everything else is
+// non-temporal as before.  keep_vecs = 0 is the kernel as it was.  The choice
+// depends on blockIdx alone: one branch ahead of the eight loads.
 constexpr int kCopyU = 8;
+// The bytes of a large copy's source that are loaded with the default policy,
+// and the smallest copy that gets them.  Measured on one MI355X
+// (tools/copy_variants.hip mall, profiles/copy_mall_split.txt; medians of three
+// sweeps): a 256 MiB source copied back to back takes 84.88 us
+// with every load non-temporal (spread of the three medians 0.20 us) and
+// 85.40 / 88.52 / 86.48 / 84.20 / 81.28 / 79.44 us with the first 32 / 64 / 96 /
+// 128 / 160 / 192 MiB kept: 192 MiB is 6.4 % faster, less than 128 MiB gains
+// nothing.  With the source rewritten before every copy all of them take 79.1 -
+// 79.8 us (no loss); a 128 MiB copy gains 7.3 %, a 64 MiB one 8.7 %.  Copies
+// below 128 MiB keep today's loads all the same: they would load everything
+// with the default policy, which costs 6 % where the source is not found in
+// the cache (profiles/r2_copy_variants.txt), and that case was not measured.
+constexpr uint64_t kCopyKeepBytes = 192ull << 20;
+constexpr uint64_t kCopyKeepMinBytes = 128ull << 20;
+
+template <bool KEEP>
+__device__ __forceinline__ void copy_tile(const u32x4 *vs, u32x4 *vd, size_t base) {
+  u32x4 x[kCopyU];
+#pragma unroll
+  for (int u = 0; u < kCopyU; u++)
+    x[u] = KEEP ? vs[base + (size_t)u * kBlock] : __builtin_nontemporal_load(vs + base + (size_t)u * kBlock);
+#pragma unroll
+  for (int u = 0; u < kCopyU; u++) __builtin_nontemporal_store(x[u], vd + base + (size_t)u * kBlock);
+}
 
 __global__ __launch_bounds__(kBlock) void k_copy(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
-                                                 size_t head, size_t nvec, size_t n) {
+                                                 size_t head, size_t nvec, size_t n, size_t keep_vecs) {
   if (blockIdx.x == 0) {
     for (size_t i = threadIdx.x; i < head; i += kBlock) dst[i] = src[i];
     for (size_t i = head + nvec * 16 + threadIdx.x; i < n; i += kBlock) dst[i] = src[i];
   }
   const u32x4 *vs = reinterpret_cast<const u32x4 *>(src + head);
   u32x4 *vd = reinterpret_cast<u32x4 *>(dst + head);
-  const size_t base = (size_t)blockIdx.x * kBlock * kCopyU + threadIdx.x;
+  const size_t tile0 = (size_t)blockIdx.x * kBlock * kCopyU, base = tile0 + threadIdx.x;
   if (base + (kCopyU - 1) * (size_t)kBlock < nvec) {
-    u32x4 x[kCopyU];
-#pragma unroll
-    for (int u = 0; u < kCopyU; u++) x[u] = __builtin_nontemporal_load(vs + base + (size_t)u * kBlock);
-#pragma unroll
-    for (int u = 0; u < kCopyU; u++) __builtin_nontemporal_store(x[u], vd + base + (size_t)u * kBlock);
+    if (tile0 < keep_vecs) {
+      // The whole tile on either side, this side between two empty asm
+      // statements (no operands, no code).  Without them the compiler merges
+      // the two sides' loads, identical but for the hint, into one set without
+      // it; with the stores shared behind the branch it reorders the loads and
+      // holds the first store back until seven of them have landed, 9 % slower.
+      asm volatile("");
+      copy_tile<true>(vs, vd, base);
+      asm volatile("");
+    } else {
+      copy_tile<false>(vs, vd, base);
+    }
   } else {
 #pragma unroll
     for (int u = 0; u < kCopyU; u++) {
@@ -622,8 +662,10 @@ int launch_copy(void *dst, const void *src, size_t bytes, void *stream) {
   const auto [head, nvec] = vec_split(dO, bytes, 1);
   const size_t tiles = (nvec + (size_t)kBlock * kCopyU - 1) / ((size_t)kBlock * kCopyU);
   const unsigned blocks = (unsigned)(tiles ? tiles : 1);
+  // BINE_COPY_KEEP_MIB in the environment, read once
+  static const CopyKeep keep = copy_keep_policy(getenv("BINE_COPY_KEEP_MIB"), kCopyKeepBytes, kCopyKeepMinBytes);
   hipLaunchKernelGGL(k_copy, dim3(blocks), dim3(kBlock), 0, st, (const uint8_t *)src, (uint8_t *)dst, head, nvec,
-                     bytes);
+                     bytes, (size_t)copy_keep_vecs(bytes, nvec, keep));
   return hipGetLastError() == hipSuccess ? BINE_SUCCESS : BINE_ERR_HIP;
 }
 

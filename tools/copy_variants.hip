@@ -4,6 +4,9 @@
 // C1 / the tail chunks (256 KiB .. 16 MiB), where launch and ramp cost dominate.
 // (3) the C2 reduce with operands staged through LDS by LDS-DMA vs the
 // library's register-only kernel.
+// (4) `copy_variants mall` (run alone): the copy with a split cache policy, part
+// of the source loaded with the default policy so that it may stay in the
+// Infinity Cache for the next call (profiles/copy_mall_split.txt).
 // Standalone program, not part of the library: variants interleaved
 // round-robin, median of rounds, HIP events on the launch stream.
 //   hipcc -O3 --offload-arch=gfx950 -I include -o copy_variants tools/copy_variants.hip \
@@ -170,6 +173,51 @@ __global__ __launch_bounds__(256) void k_red_lds(const f4 *__restrict__ a, const
   }
 }
 
+// split cache policy (part 4, `copy_variants mall`): the library's k_copy shape
+// (256 x 8 vectors per workgroup), loads of tiles whose first vector lies below
+// `keep_vecs` with the default policy, every other load and every store
+// non-temporal.  The choice is uniform over the workgroup (blockIdx only): one
+// scalar branch ahead of the eight loads.  keep_vecs = 0 is the library's kernel.
+__global__ __launch_bounds__(256) void k_copy_split(const u4 *__restrict__ a, u4 *__restrict__ o, size_t nvec,
+                                                    size_t keep_vecs) {
+  constexpr int BS = 256, U = 8;
+  const size_t tile0 = (size_t)blockIdx.x * BS * U, base = tile0 + threadIdx.x;
+  if (base + (U - 1) * (size_t)BS < nvec) {
+    u4 x[U];
+    if (tile0 < keep_vecs) {
+      // the whole tile on either side, this side fenced by two empty asm
+      // statements (no operands, no code): without them the compiler merges
+      // the two sides' loads, identical but for the hint, into one set without
+      // it; with the stores shared behind the branch it reorders the loads
+      // and holds the first store back until seven of them have landed
+      asm volatile("");
+#pragma unroll
+      for (int u = 0; u < U; u++) x[u] = a[base + (size_t)u * BS];
+#pragma unroll
+      for (int u = 0; u < U; u++) __builtin_nontemporal_store(x[u], o + base + (size_t)u * BS);
+      asm volatile("");
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; u++) x[u] = __builtin_nontemporal_load(a + base + (size_t)u * BS);
+#pragma unroll
+      for (int u = 0; u < U; u++) __builtin_nontemporal_store(x[u], o + base + (size_t)u * BS);
+    }
+  } else {
+    for (int u = 0; u < U; u++) {
+      const size_t i = base + (size_t)u * BS;
+      if (i < nvec) o[i] = a[i];
+    }
+  }
+}
+
+// the producer of pattern (b): rewrites the whole buffer with ordinary stores
+__global__ __launch_bounds__(256) void k_produce(u4 *__restrict__ a, size_t nvec, unsigned tag) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
+    const unsigned lo = (unsigned)i * 2654435761u + tag;
+    a[i] = u4{lo, lo ^ 0x9e3779b9u, (unsigned)(i >> 32) + tag, lo * 31u + 7u};
+  }
+}
+
 struct Var {
   std::string name;
   std::function<void(int, hipStream_t)> run;  // argument: buffer set
@@ -180,10 +228,126 @@ static double median(std::vector<float> v) {
   return v[v.size() / 2];
 }
 
+// ---- (4) split cache policy: does a bounded part of a large copy's source,
+// loaded with the default policy while everything else goes non-temporally,
+// stay in the 256 MiB Infinity Cache until the next copy of the same source?
+// R = bytes loaded with the default policy.  Patterns:
+//   (a) the benchmark's: one 256 MiB source copied back to back
+//   (b) a producer kernel rewrites the whole source (ordinary stores) before
+//       every copy; the copy alone is timed
+//   (c) a 64 MiB copy back to back (R clipped to the size), and a 128 MiB one
+//       (the smallest copy the library gives the policy to)
+// bench.py's statistic: an event pair per launch, 5 warm-up + 20 timed
+// launches, the first 20 % of the timed ones dropped, the median.  The R
+// values alternate inside one process; the whole sweep runs three times.  The
+// decision rule is printed with its inputs.
+static int mall_split(hipStream_t s) {
+  const size_t MiB = (size_t)1 << 20;
+  // variant 0 is the control, the library's kernel itself (no branch); variant 1
+  // the split kernel with nothing kept: what the branch alone costs
+  const size_t Rs[] = {0, 0, 32, 64, 96, 128, 160, 192};
+  static const char *vname[] = {"R=  0 (library)", "R=  0 (split)  ", "R= 32 MiB      ", "R= 64 MiB      ",
+                                "R= 96 MiB      ", "R=128 MiB      ", "R=160 MiB      ", "R=192 MiB      "};
+  const int nR = 8, sweeps = 3, warm = 5, steps = 20;
+  const size_t big = 256 * MiB, psize[4] = {big, big, 64 * MiB, 128 * MiB};
+  u4 *A, *O;
+  CK(hipMalloc(&A, big));
+  CK(hipMalloc(&O, big));
+  std::vector<hipEvent_t> ev0(steps), ev1(steps);
+  for (int i = 0; i < steps; i++) {
+    CK(hipEventCreate(&ev0[i]));
+    CK(hipEventCreate(&ev1[i]));
+  }
+  auto copy = [&](size_t bytes, int v) {
+    const size_t nvec = bytes / 16, tiles = (nvec + 2047) / 2048;
+    if (v == 0)
+      hipLaunchKernelGGL((k_copy_tile<256, 8, 1, 1, 1>), dim3((unsigned)tiles), dim3(256), 0, s, A, O, nvec);
+    else
+      hipLaunchKernelGGL(k_copy_split, dim3((unsigned)tiles), dim3(256), 0, s, A, O, nvec,
+                         std::min(Rs[v] * MiB, bytes) / 16);
+  };
+  unsigned tag = 0;
+  // median (us) of the kept per-launch times of one (pattern, R) run
+  auto run = [&](int pat, int v, double *us) -> int {
+    const size_t bytes = psize[pat];
+    for (int i = 0; i < warm + steps; i++) {
+      if (pat == 1) hipLaunchKernelGGL(k_produce, dim3(2048), dim3(256), 0, s, A, bytes / 16, ++tag);
+      if (i >= warm) CK(hipEventRecord(ev0[i - warm], s));
+      copy(bytes, v);
+      if (i >= warm) CK(hipEventRecord(ev1[i - warm], s));
+    }
+    CK(hipStreamSynchronize(s));
+    std::vector<float> t(steps);
+    for (int i = 0; i < steps; i++) CK(hipEventElapsedTime(&t[i], ev0[i], ev1[i]));
+    *us = median(std::vector<float>(t.begin() + steps / 5, t.end())) * 1e3;
+    return 0;
+  };
+  static const char *pname[4] = {"(a) 256 MiB, same source back to back", "(b) 256 MiB, source rewritten before every copy",
+                                 "(c) 64 MiB, same source back to back", "(c) 128 MiB, same source back to back"};
+  double med[4][8][3];
+  for (int w = 0; w < sweeps; w++)
+    for (int pat = 0; pat < 4; pat++) {
+      if (pat != 1) bine_fill_pico(A, psize[pat] / 4, BINE_FLOAT, 1234, nullptr);
+      CK(hipDeviceSynchronize());
+      for (int r = 0; r < nR; r++) {
+        if (run(pat, r, &med[pat][r][w])) return 1;
+        const size_t bytes = psize[pat];
+        printf("sweep %d %-48s %s  us=%8.2f  2S/t GB/s=%8.1f\n", w + 1, pname[pat], vname[r], med[pat][r][w],
+               2.0 * bytes / (med[pat][r][w] * 1e-6) / 1e9);
+      }
+    }
+  // every R copies the same bytes (pattern (a)'s data)
+  {
+    std::vector<unsigned> h(big / 4), g(big / 4);
+    bine_fill_pico(A, big / 4, BINE_FLOAT, 1234, nullptr);
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(h.data(), A, big, hipMemcpyDeviceToHost));
+    int bad = 0;
+    for (int r = 0; r < nR; r++) {
+      CK(hipMemset(O, 0, big));
+      copy(big, r);
+      CK(hipStreamSynchronize(s));
+      CK(hipMemcpy(g.data(), O, big, hipMemcpyDeviceToHost));
+      if (g != h) bad++, printf("MISMATCH %s\n", vname[r]);
+    }
+    printf("bytes copied equal the source for %d of %d variants\n", nR - bad, nR);
+  }
+  // summary and decision
+  double m3[4][8], spread0[4];
+  for (int pat = 0; pat < 4; pat++) {
+    printf("== %s: medians of the three sweeps (us), their median\n", pname[pat]);
+    for (int r = 0; r < nR; r++) {
+      double *m = med[pat][r];
+      m3[pat][r] = std::max(std::min(m[0], m[1]), std::min(std::max(m[0], m[1]), m[2]));
+      printf("%s  %8.2f %8.2f %8.2f   median %8.2f   vs library %+6.2f %%\n", vname[r], m[0], m[1], m[2], m3[pat][r],
+             100.0 * (m3[pat][r] / m3[pat][0] - 1.0));
+    }
+    spread0[pat] = *std::max_element(med[pat][0], med[pat][0] + 3) - *std::min_element(med[pat][0], med[pat][0] + 3);
+    printf("spread of R=0's three medians: %.2f us (%.2f %%)\n", spread0[pat], 100.0 * spread0[pat] / m3[pat][0]);
+  }
+  int best = 2;
+  for (int r = 3; r < nR; r++)
+    if (m3[0][r] < m3[0][best]) best = r;
+  const bool wins = m3[0][0] - m3[0][best] > 3.0 * spread0[0];
+  const bool b_ok = m3[1][best] <= m3[1][0] + spread0[1];
+  const bool c_ok = m3[2][best] <= m3[2][0] + spread0[2] && m3[3][best] <= m3[3][0] + spread0[3];
+  printf("== decision: fastest R > 0 on (a) is %zu MiB: %.2f us against R=0 %.2f us, gain %.2f us, needs > 3 x %.2f "
+         "= %.2f us: %s; (b) %.2f against %.2f + %.2f: %s; (c) 64 MiB %.2f against %.2f + %.2f, 128 MiB %.2f against "
+         "%.2f + %.2f: %s\n",
+         Rs[best], m3[0][best], m3[0][0], m3[0][0] - m3[0][best], spread0[0], 3.0 * spread0[0], wins ? "yes" : "no",
+         m3[1][best], m3[1][0], spread0[1], b_ok ? "not slower" : "SLOWER", m3[2][best], m3[2][0], spread0[2],
+         m3[3][best], m3[3][0], spread0[3], c_ok ? "not slower" : "SLOWER");
+  printf("== %s\n", wins && b_ok && c_ok ? "ADOPT this R" : "NO R qualifies: the library's kernel stays as it is");
+  CK(hipFree(A));
+  CK(hipFree(O));
+  return 0;
+}
+
 int main(int argc, char **argv) {
   const int rounds = 7, iters = 20;
   hipStream_t s;
   CK(hipStreamCreate(&s));
+  if (argc > 1 && std::string(argv[1]) == "mall") return mall_split(s);  // part 4 alone
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
