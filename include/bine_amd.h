@@ -584,6 +584,102 @@ int bine_step_update(void *state, const double *norm2, const bine_step_hyper *hy
 int bine_adamw_segments_dyn(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
                             void *const *pout, const size_t *counts, int gdtype, int odtype, const void *state,
                             void *stream);
+/* ---- FP8 quantization of a list of tensors with per-tensor scaling ---------------
+ * "Current scaling": the largest magnitude of each tensor, a power-of-two scale
+ * from it, the tensor times that scale in OCP FP8 (the gfx950 encodings, not
+ * the MI300X fnuz ones), one byte per element; bine_quant_multi (below, with
+ * the collectives) does that for a sharded bucket and gathers the bytes.
+ * Formats (fmt): BINE_FP8_E4M3 -- e4m3fn: 4 exponent bits, bias 7, no infinity,
+ * S.1111.111 the only NaN, largest finite 448 -- and BINE_FP8_E5M2 -- IEEE-like,
+ * bias 15, largest finite 57344.  FMAX = 0.875 * 2^fe, fe = 9 resp. 16.
+ * Wide element types (dtype, sdtype, ddtype): BINE_FLOAT, BINE_FLOAT16,
+ * BINE_BFLOAT16.  widen() is the exact conversion to binary32 as a map of bit
+ * patterns: a 16-bit NaN keeps its sign and its payload, shifted, and is not
+ * quieted.  All device calls are stream-ordered, without host synchronization
+ * and without allocation; ordinary launches, never captured.
+ *
+ * bine_amax_segments: out[k] = the maximum over tensor k's elements of
+ * bits(widen(x)) & 0x7fffffff, compared as unsigned integers: the bit pattern
+ * of the largest |x|; any NaN pattern is above +inf's, so a NaN anywhere shows.
+ * An empty tensor gives 0 (its pointer may be NULL).  `out`: n uint32 on the
+ * device.  Integer maximum has no order: the bits depend on the data alone.
+ * Mechanism: out is zeroed in stream (k_amax_zero), then k_amax_segs over the
+ * sum-of-squares calls' tile table of the buffers (32 KiB tiles of 16-B
+ * aligned vectors, here BINE_AMAX_TILES_PER_WG consecutive tiles of a tensor
+ * per workgroup, at least one workgroup per non-empty tensor, a tensor's
+ * first workgroup also taking the elements before the first and after the
+ * last vector; a full tile's loads all issued before its first use); the
+ * 16-bit types compare their 15-bit patterns, which widening keeps in order,
+ * and widen the winner once; at most one atomic maximum per workgroup on
+ * out[k] (none where the workgroup's winner is not above what out[k] holds).
+ * BINE_ERR_ARG, before any HIP call, in this order: dtype; n < 0 or n >
+ * BINE_MULTI_MAX; bufs or counts NULL with n > 0; a NULL buffer with a
+ * non-zero count; a buffer not aligned to its element size; out NULL or not
+ * 4-byte aligned.
+ *
+ * The scale rule (bine_fp8_scale_host, and bine_fp8_scales on the device: ONE
+ * inline function compiled for both, pico_amd/csrc/bine_internal.h), integer
+ * arithmetic on the pattern:
+ *   if bits == 0 or bits >= 0x7f800000:  e = 0        (all zero; inf or NaN)
+ *   else: the value is f * 2^x with f in [0.5, 1)     (frexp; subnormals too)
+ *         e = fe - x - (f > 0.875 ? 1 : 0);  e = min(max(e, -126), 126)
+ *   scale = 2^e;  inv = 2^-e
+ * e is the largest exponent with amax * 2^e <= FMAX, clamped to where the
+ * scale and its inverse are both normal; the products with it are exact.
+ * bine_fp8_scales: amax = n uint32 on the device, scales = 2n floats on the
+ * device, scales[k] = the scale and scales[n + k] its inverse; one launch of
+ * k_fp8_scales.  BINE_ERR_ARG, before any HIP call: fmt; n < 0 or n >
+ * BINE_MULTI_MAX; amax or scales NULL or not 4-byte aligned (bine_fp8_scale_host:
+ * fmt; scale or inv NULL).
+ *
+ * bine_quant_segments: dst8[k][i] = encode(widen(src[k][i]) * scales[k]); scales
+ * = n floats on the device (bine_fp8_scales' first half), NULL meaning 1.  Per
+ * element:
+ *   y = widen(x) * s          one binary32 multiplication, subnormals kept,
+ *                             nothing contracted
+ *   y is NaN:  the byte 0x7F
+ *   otherwise  y = min(max(y, -FMAX), FMAX) (so +-inf saturates), then y
+ *              rounded to nearest even into the format, its subnormals kept
+ *              and the sign of zero kept
+ * dst8[k] may have any byte alignment.  Source and destination ranges must not
+ * overlap (not checked).  Mechanism: k_quant_segs over the same tile table of
+ * the SOURCE, 128 descriptors per launch by value; the rounding is gfx950's
+ * packed conversion (v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32) behind the NaN select
+ * and the clamp.  With h = the elements before src's first 16-B boundary, a
+ * segment whose dst8 + h is aligned to the bytes one source vector yields (4
+ * for float, 8 for the 16-bit types) takes the vector body (whole 4- or 8-byte
+ * non-temporal stores); any other takes the element body, the same operations
+ * through byte stores, the same bits.  BINE_ERR_ARG, before any HIP call, in
+ * this order: sdtype or fmt; n < 0 or n > BINE_MULTI_MAX; src, dst8 or counts
+ * NULL with n > 0; a NULL buffer with a non-zero count; a source not aligned
+ * to its element size; scales not 4-byte aligned.
+ *
+ * bine_dequant_segments: dst[k][i] = narrow(decode(src8[k][i]) * inv_scales[k]);
+ * inv_scales = n floats on the device (bine_fp8_scales' second half), NULL
+ * meaning 1.  decode is exact (integer arithmetic); one binary32
+ * multiplication; narrow rounds once to nearest even for the 16-bit types.  A
+ * NaN byte gives the destination type's quiet NaN 0x7fc00000 / 0x7e00 / 0x7fc0
+ * with the byte's sign, whatever the scale.  The tile table is the
+ * DESTINATION's; bodies and refusals as bine_quant_segments with the roles
+ * swapped (the same kernel, k_quant_segs' dequantizing form).
+ *
+ * bine_plan_quant (host only): the launches bine_quant_segments issues for
+ * these source and destination addresses (bine_dequant_segments: pass dst as
+ * `wide` and src8 as `bytes8`).  Returns the number of non-empty segments (may
+ * exceed cap) or -status; with `out`, one record of 5 uint64 per non-empty
+ * segment, in launch order: (launch, segment, its first workgroup in the
+ * launch, its workgroups, body: 0 vector / 1 element). */
+typedef enum { BINE_FP8_E4M3 = 0, BINE_FP8_E5M2 = 1 } bine_fp8_format_t;
+#define BINE_AMAX_TILES_PER_WG 4
+int bine_amax_segments(int n, const void *const *bufs, const size_t *counts, int dtype, uint32_t *out, void *stream);
+int bine_fp8_scale_host(uint32_t amax_bits, int fmt, float *scale, float *inv);
+int bine_fp8_scales(int n, const uint32_t *amax, int fmt, float *scales, void *stream);
+int bine_quant_segments(int n, const void *const *src, void *const *dst8, const size_t *counts, int sdtype, int fmt,
+                        const float *scales, void *stream);
+int bine_dequant_segments(int n, const void *const *src8, void *const *dst, const size_t *counts, int ddtype,
+                          int fmt, const float *inv_scales, void *stream);
+int64_t bine_plan_quant(int n, const uint64_t *wide, const uint64_t *bytes8, const size_t *counts, int dtype,
+                        uint64_t *out, int64_t cap);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -1062,6 +1158,40 @@ int bine_adamw_multi(bine_comm_t comm, int ag_algo, int n, void *const *params, 
 int bine_adamw_multi_dyn(bine_comm_t comm, int ag_algo, int n, void *const *params, void *const *p, void *const *m,
                          void *const *v, const void *const *g, const size_t *shard_counts, int gdtype, int odtype,
                          const void *state, void *stream);
+/* ---- FP8 quantized parameter allgather of a bucket -------------------------------
+ * What follows the step where the consumers take 1-byte weights: params8[k] is
+ * the full FP8 tensor, comm size * shard_counts[k] bytes; src[k] is this rank's
+ * shard (shard_counts[k] elements of sdtype -- typically the float32 master p
+ * bine_adamw_segments has just written); scales = 2n floats on the device, on
+ * return scales[k] = tensor k's scale and scales[n + k] its inverse, the same
+ * bits on every rank.  The allgather moves 1 byte per element where
+ * bine_adamw_multi's moves 2.  Bit for bit this sequence, all on the caller's
+ * stream:
+ *   1. bine_amax_segments(n, src, shard_counts, sdtype, V): V = n uint32 in the
+ *      communicator's multi workspace;
+ *   2. bine_allreduce(comm, amax_algo, BINE_IN_PLACE, V, n, BINE_UINT32, BINE_MAX,
+ *      segsize 0): every rank holds each tensor's largest pattern;
+ *   3. bine_fp8_scales(n, V, fmt, scales);
+ *   4. bine_quant_segments with dst8[k] = params8[k] + rank * shard_counts[k];
+ *   5. bine_allgather_multi(comm, ag_algo, n, NULL (in place), params8,
+ *      shard_counts, BINE_UINT8).
+ * A NaN or an infinity in any rank's shard of a tensor gives that tensor scale
+ * 1 on every rank (the rule's e = 0).  The kernels of 1, 3 and 4 are ordinary
+ * launches, never captured; with graph mode on the inner collectives replay
+ * as any call on those addresses.  With n = 0 or every shard count 0 the call
+ * succeeds and writes nothing.  Refusals, before any exchange and any HIP
+ * call, in this order: sdtype or fmt; n < 0 or n > BINE_MULTI_MAX; params8, src
+ * or shard_counts NULL with n > 0; a NULL buffer with a non-zero count; a
+ * source not aligned to its element size; scales NULL or not 4-byte aligned;
+ * a shard count above INT_MAX (all BINE_ERR_ARG); amax_algo outside the
+ * allreduce range or ag_algo outside the allgather range
+ * (BINE_ERR_UNSUPPORTED); comm == NULL (BINE_ERR_ARG).  Steps 2 and 5 return
+ * whatever the single calls refuse.  Not provided: delayed scaling (the store
+ * fused into k_adamw_segs), amax histories, block or MX scaling, FP8 gradients
+ * in the reduce-scatter. */
+int bine_quant_multi(bine_comm_t comm, int amax_algo, int ag_algo, int n, void *const *params8,
+                     const void *const *src, const size_t *shard_counts, int sdtype, int fmt, float *scales,
+                     void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -1170,6 +1300,12 @@ int bine_loopback_run_adamw_multi_dyn(bine_comm_t *comms, int nranks, int ag_alg
                                       void *const *p, void *const *m, void *const *v, const void *const *g,
                                       const size_t *shard_counts, int gdtype, int odtype,
                                       const void *const *states, int *statuses);
+/* bine_quant_multi on every virtual rank: params8 and src hold nranks * n
+ * entries, rank r's tensor k at [r * n + k]; shard_counts n entries (every
+ * rank's); scales one device pointer (2n floats) per rank */
+int bine_loopback_run_quant_multi(bine_comm_t *comms, int nranks, int amax_algo, int ag_algo, int n,
+                                  void *const *params8, const void *const *src, const size_t *shard_counts,
+                                  int sdtype, int fmt, float *const *scales, int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

@@ -80,6 +80,11 @@ class OpTime(ctypes.Structure):
                 ("start_ms", ctypes.c_float), ("ms", ctypes.c_float)]
 
 
+# bine_fp8_format_t: the OCP FP8 encodings of bine_quant_segments, and their largest finite values
+FP8_FORMATS = {"e4m3": 0, "e5m2": 1}
+FP8_MAX = {"e4m3": 448.0, "e5m2": 57344.0}
+
+
 # the step state of bine_step_update (BINE_STEP_STATE_BYTES: 8 doubles, 8 floats)
 STEP_STATE_BYTES = 96
 
@@ -214,6 +219,14 @@ def lib():
         "bine_adamw_segments_dyn": ([i, vp, vp, vp, vp, vp, vp, i, i, vp, vp], i),
         "bine_adamw_multi_dyn": ([vp, i, i, vp, vp, vp, vp, vp, vp, i, i, vp, vp], i),
         "bine_loopback_run_adamw_multi_dyn": ([vp, i, i, i, vp, vp, vp, vp, vp, vp, i, i, vp, vp], i),
+        "bine_amax_segments": ([i, vp, vp, i, vp, vp], i),
+        "bine_fp8_scale_host": ([u32, i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)], i),
+        "bine_fp8_scales": ([i, vp, i, vp, vp], i),
+        "bine_quant_segments": ([i, vp, vp, vp, i, i, vp, vp], i),
+        "bine_dequant_segments": ([i, vp, vp, vp, i, i, vp, vp], i),
+        "bine_plan_quant": ([i, vp, vp, vp, i, vp, ctypes.c_int64], ctypes.c_int64),
+        "bine_quant_multi": ([vp, i, i, i, vp, vp, vp, i, i, vp, vp], i),
+        "bine_loopback_run_quant_multi": ([vp, i, i, i, i, vp, vp, vp, i, i, vp, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

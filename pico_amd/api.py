@@ -1053,6 +1053,142 @@ def loopback_adamw_multi_dyn(comms, ag_algo, params, p, m, v, g, states, gdtype=
     return rc, list(st)
 
 
+# ---- FP8 quantization of a bucket with per-tensor scaling -----------------------------------
+
+def _fp8(fmt) -> int:
+    return fmt if isinstance(fmt, int) else _lib.FP8_FORMATS[fmt]
+
+
+def _dev_of(bufs):
+    return next((b.device for b in bufs if hasattr(b, "device")), "cuda")
+
+
+def amax_segments(bufs, dtype=None, counts=None, out=None, stream=None):
+    """out[k] = the bit pattern of tensor k's largest |x| widened to float32
+    (bine_amax_segments): the maximum of bits(x) & 0x7fffffff as unsigned
+    integers, so any NaN shows as a pattern above infinity's and an empty tensor
+    gives 0.  float / float16 / bfloat16; empty tensors may be None.  `out`: n
+    int32 on the device holding the uint32 patterns (allocated when None).
+    Returns out."""
+    n = len(bufs)
+    c = _norm_counts("amax_segments", bufs, counts)
+    if out is None:
+        import torch
+        out = torch.empty(max(n, 1), dtype=torch.int32, device=_dev_of(bufs))
+    check(lib().bine_amax_segments(n, _ptrs(bufs), c, _adamw_dtype(dtype, bufs), _ptr(out), _stream(stream, None)),
+          "bine_amax_segments")
+    return out
+
+
+def fp8_scale_host(amax_bits: int, fmt):
+    """(scale, inverse) for one amax pattern (bine_fp8_scale_host, host only):
+    scale = 2^e with e the largest exponent for which amax * 2^e <= FMAX (448
+    for "e4m3", 57344 for "e5m2"), clamped to [-126, 126]; e = 0 for an all-zero
+    tensor and for inf / NaN."""
+    s, i = ctypes.c_float(), ctypes.c_float()
+    check(lib().bine_fp8_scale_host(int(amax_bits) & 0xFFFFFFFF, _fp8(fmt), ctypes.byref(s), ctypes.byref(i)),
+          "bine_fp8_scale_host")
+    return s.value, i.value
+
+
+def fp8_scales(amax, fmt, n: int, scales=None, stream=None):
+    """scales[k] = the scale of amax[k], scales[n + k] its inverse, on the device
+    (bine_fp8_scales; the rule of fp8_scale_host).  amax: the n patterns
+    amax_segments wrote (int32 tensor or address; n is the caller's, a tensor
+    allocated for an empty list still has one word); scales: 2n float32
+    (allocated when None).  Returns scales."""
+    if scales is None:
+        import torch
+        scales = torch.empty(max(2 * n, 1), dtype=torch.float32, device=_dev_of([amax]))
+    check(lib().bine_fp8_scales(n, _ptr(amax), _fp8(fmt), _ptr(scales), _stream(stream, None)), "bine_fp8_scales")
+    return scales
+
+
+def plan_quant(wide: Sequence[int], bytes8: Sequence[int], counts: Sequence[int], dtype):
+    """The launches of quant_segments for these source (`wide`) and destination
+    (`bytes8`) addresses -- of dequant_segments with the destination as `wide`
+    -- (bine_plan_quant, host only): a list of (launch, segment, first workgroup
+    in the launch, workgroups, body) per non-empty segment, body 0 = vector,
+    1 = element."""
+    n = len(counts)
+    if len(wide) != n or len(bytes8) != n:
+        raise ValueError("plan_quant: the address lists and counts differ in length")
+    arr = lambda a: (ctypes.c_uint64 * max(n, 1))(*a)  # noqa: E731
+    args = (n, arr(wide), arr(bytes8), (ctypes.c_size_t * max(n, 1))(*counts), _adamw_dtype(dtype, ()))
+    cap = lib().bine_plan_quant(*args, None, 0)
+    if cap < 0:
+        raise BineError(int(-cap), "bine_plan_quant")
+    out = (ctypes.c_uint64 * (5 * max(cap, 1)))()
+    lib().bine_plan_quant(*args, out, cap)
+    return [tuple(out[5 * t:5 * t + 5]) for t in range(cap)]
+
+
+def quant_segments(src, dst8, fmt, scales=None, sdtype=None, counts=None, stream=None) -> None:
+    """dst8[k] = tensor src[k] times scales[k] in OCP FP8, one byte per element
+    (bine_quant_segments): one float32 multiplication, NaN -> 0x7F, everything
+    else clamped to +-FMAX and rounded to nearest even.  src float / float16 /
+    bfloat16; dst8 uint8 at any byte alignment; scales: n float32 on the device
+    (fp8_scales' first half), None = 1.  Empty tensors may be None."""
+    if len(src) != len(dst8):
+        raise ValueError("quant_segments: src and dst8 differ in length")
+    c = _norm_counts("quant_segments", src, counts)
+    check(lib().bine_quant_segments(len(src), _ptrs(src), _ptrs(dst8), c, _adamw_dtype(sdtype, src), _fp8(fmt),
+                                    _ptr(scales), _stream(stream, None)), "bine_quant_segments")
+
+
+def dequant_segments(src8, dst, fmt, inv_scales=None, ddtype=None, counts=None, stream=None) -> None:
+    """dst[k] = the FP8 bytes src8[k] decoded exactly, times inv_scales[k] in
+    float32, rounded once into dst's type (bine_dequant_segments).  inv_scales:
+    n float32 on the device (fp8_scales' second half), None = 1."""
+    if len(src8) != len(dst):
+        raise ValueError("dequant_segments: src8 and dst differ in length")
+    c = _norm_counts("dequant_segments", dst, counts)
+    check(lib().bine_dequant_segments(len(dst), _ptrs(src8), _ptrs(dst), c, _adamw_dtype(ddtype, dst), _fp8(fmt),
+                                      _ptr(inv_scales), _stream(stream, None)), "bine_dequant_segments")
+
+
+def quant_multi(amax_algo, ag_algo, params8, src, fmt, comm: Comm, scales=None, sdtype=None, shard_counts=None,
+                stream=None):
+    """bine_quant_multi: this rank's shards src[k] quantized with one scale per
+    tensor agreed over all ranks, and the bytes gathered into params8[k]
+    (comm.size * shard_counts[k] uint8) -- bit for bit amax_segments, one
+    in-place allreduce (uint32, max) of the patterns, fp8_scales, quant_segments
+    into this rank's slots, allgather_multi in place as uint8.  scales: 2n
+    float32 on the device (allocated when None), the same bits on every rank.
+    Returns scales."""
+    if len(params8) != len(src):
+        raise ValueError("quant_multi: params8 and src differ in length")
+    n = len(src)
+    c = _norm_counts("quant_multi", src, shard_counts)
+    if scales is None:
+        import torch
+        scales = torch.empty(max(2 * n, 1), dtype=torch.float32, device=_dev_of(src))
+    check(lib().bine_quant_multi(comm.handle, _algo("allreduce", amax_algo), _algo("allgather", ag_algo), n,
+                                 _ptrs(params8), _ptrs(src), c, _adamw_dtype(sdtype, src), _fp8(fmt), _ptr(scales),
+                                 _stream(stream, comm)), f"quant_multi ({amax_algo}, {ag_algo})")
+    return scales
+
+
+def loopback_quant_multi(comms, amax_algo, ag_algo, params8, src, fmt, scales, sdtype=None, shard_counts=None):
+    """quant_multi on every virtual rank: params8 and src one list of tensors
+    per rank, shard_counts one list for all ranks (None: rank 0's numel()),
+    scales one device float32 buffer of 2n per rank.  Returns (status, per-rank
+    statuses)."""
+    P = len(comms)
+    n = len(src[0])
+    if any(len(x) != P for x in (params8, src, scales)) or any(len(r) != n for x in (params8, src) for r in x):
+        raise ValueError("loopback_quant_multi: the ranks' lists differ in length")
+    if shard_counts is None:
+        shard_counts = [t.numel() for t in src[0]]
+    flat = lambda x: [t for r in x for t in r]  # noqa: E731
+    st = (ctypes.c_int * P)()
+    hs = (ctypes.c_void_p * P)(*[c.handle.value for c in comms])
+    rc = lib().bine_loopback_run_quant_multi(
+        hs, P, _algo("allreduce", amax_algo), _algo("allgather", ag_algo), n, _ptrs(flat(params8)), _ptrs(flat(src)),
+        (ctypes.c_size_t * max(n, 1))(*shard_counts), _adamw_dtype(sdtype, flat(src)), _fp8(fmt), _ptrs(scales), st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -1448,6 +1584,8 @@ __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fus
            "adamw_consts", "plan_adamw", "adamw_segments", "adamw_multi", "loopback_adamw_multi",
            "step_state_init", "step_update_host", "step_update", "step_state_read", "adamw_segments_dyn",
            "adamw_multi_dyn", "loopback_adamw_multi_dyn",
+           "amax_segments", "fp8_scales", "fp8_scale_host", "quant_segments", "dequant_segments", "plan_quant",
+           "quant_multi", "loopback_quant_multi",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

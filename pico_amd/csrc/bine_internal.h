@@ -428,6 +428,76 @@ int adamw_dyn_args(int n, void *const *p, void *const *m, void *const *v, const 
 int launch_adamw_segments_dyn_h16(int n, void *const *p, void *const *m, void *const *v, const void *const *g,
                                   void *const *pout, const size_t *counts, int gdtype, int odtype, const void *state,
                                   void *stream);
+
+// FP8 quantization of a list of tensors (bine_amax_segments, bine_fp8_scales,
+// bine_quant_segments, bine_dequant_segments; kernels_h16.o).
+// The scale rule of bine_amd.h -- ONE statement for the host twin
+// (bine_fp8_scale_host, segments.cpp) and for k_fp8_scales (kernels.hip), in
+// integer arithmetic on the pattern; tests/fp8_sim.py restates it with frexp.
+constexpr int fp8_fe(int fmt) { return fmt == BINE_FP8_E4M3 ? 9 : 16; }  // FMAX = 0.875 * 2^fe
+inline bool fp8_fmt_ok(int fmt) { return fmt == BINE_FP8_E4M3 || fmt == BINE_FP8_E5M2; }
+BINE_HOST_DEVICE inline void fp8_scale_rule(uint32_t bits, int fmt, float *scale, float *inv) {
+  int e = 0;
+  if (bits != 0 && bits < 0x7f800000u) {
+    // the value as f * 2^x, f = 1.frac / 2 in [0.5, 1)
+    const uint32_t ex = bits >> 23, man = bits & 0x7fffffu;
+    int x;
+    uint32_t frac;
+    if (ex) {
+      x = (int)ex - 126;
+      frac = man;
+    } else {  // subnormal: man * 2^-149 with its leading one at bit p
+      const int p = 31 - __builtin_clz(man);
+      x = p - 148;
+      frac = (man << (23 - p)) & 0x7fffffu;
+    }
+    e = fp8_fe(fmt) - x - (frac > 0x600000u ? 1 : 0);  // f > 0.875
+    e = e < -126 ? -126 : e > 126 ? 126 : e;
+  }
+  const uint32_t sb = (uint32_t)(127 + e) << 23, ib = (uint32_t)(127 - e) << 23;
+  __builtin_memcpy(scale, &sb, 4);
+  __builtin_memcpy(inv, &ib, 4);
+}
+// k_quant_segs, both directions: plan_norm_launches' table over the WIDE side
+// (the source of a quantization, the destination of a dequantization) -- the
+// same tiles, the same first-workgroup rule -- with one flag per slot
+struct QuantLaunch : LaunchTable<kSegsPerLaunch> {
+  uint64_t elem[(kSegsPerLaunch + 63) / 64] = {};  // bit s: slot s takes the element body
+};
+// k_amax_segs: the same table with kAmaxTilesPerWg consecutive tiles of a slot
+// per workgroup (tile0 counts workgroups: ceil(tiles / kAmaxTilesPerWg) per
+// slot).  Every workgroup ends in a look at out[k] and, where it holds a new
+// maximum, an atomic on that one address; atomics on one address serialise,
+// and with a workgroup per tile the thousands that end together before any
+// maximum is visible cost 20 us on a 256 MiB tensor (tools/amax_variants.hip,
+// DESIGN.md 6.9).
+constexpr uint32_t kAmaxTilesPerWg = BINE_AMAX_TILES_PER_WG;
+using AmaxLaunch = LaunchTable<kSegsPerLaunch>;
+AmaxLaunch amax_launch_of(const LaunchTable<kSegsPerLaunch> &tiles);
+// the body flags of `ls` (plan_quant_launches' tables of `wide`) for another byte side
+void quant_set_bodies(std::vector<QuantLaunch> &ls, const void *const *wide, const void *const *bytes8, int dtype);
+// The checks of the two lists that need no device, in the header's order (dtype
+// through the source's alignment), then the launches.  With h = the elements
+// before wide's first 16-B boundary a slot takes the vector body where bytes8
+// + h is aligned to 16 / esz bytes (what one wide vector holds in FP8).
+int plan_quant_launches(int n, const uint64_t *wide, const uint64_t *bytes8, const size_t *counts, int dtype,
+                        std::vector<QuantLaunch> &out);
+// Every check of the four entry points, nothing launched; BINE_SUCCESS or
+// BINE_ERR_ARG with *why = what was refused.  ls: the launches, where given.
+int amax_args(int n, const void *const *bufs, const size_t *counts, int dtype, const void *out, const char **why,
+              std::vector<AmaxLaunch> *ls);
+int fp8_scales_args(int n, const void *amax, int fmt, const void *scales, const char **why);
+// wide / bytes8: src / dst8 of bine_quant_segments, dst / src8 of bine_dequant_segments
+int quant_args(int n, const void *const *wide, const void *const *bytes8, const size_t *counts, int dtype, int fmt,
+               const void *scales, const char **why, std::vector<QuantLaunch> *ls);
+// the launches themselves (arguments checked by the functions above)
+int launch_amax_segments_h16(const std::vector<AmaxLaunch> &ls, int n, const void *const *bufs, const size_t *counts,
+                             int dtype, uint32_t *out, void *stream);
+int launch_fp8_scales_h16(int n, const uint32_t *amax, int fmt, float *scales, void *stream);
+int launch_quant_segments_h16(const std::vector<QuantLaunch> &ls, const void *const *src, void *const *dst8,
+                              const size_t *counts, int sdtype, int fmt, const float *scales, void *stream);
+int launch_dequant_segments_h16(const std::vector<QuantLaunch> &ls, const void *const *src8, void *const *dst,
+                                const size_t *counts, int ddtype, int fmt, const float *inv_scales, void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -2077,6 +2077,43 @@ int bine_adamw_segments_dyn(int n, void *const *p, void *const *m, void *const *
   return launch_adamw_segments_dyn_h16(n, p, m, v, g, pout, counts, gdtype, odtype, state, stream);  // likewise
 }
 
+// a refusal of the FP8 calls: the status, with the reason left in bine_last_error
+static int fp8_refused(const char *fn, int rc, const char *why) {
+  if (rc) set_err("%s: %s", fn, why ? why : bine_status_string(rc));
+  return rc;
+}
+
+int bine_amax_segments(int n, const void *const *bufs, const size_t *counts, int dtype, uint32_t *out, void *stream) {
+  const char *why = nullptr;
+  std::vector<AmaxLaunch> ls;
+  if (const int rc = amax_args(n, bufs, counts, dtype, out, &why, &ls)) return fp8_refused(__func__, rc, why);
+  return launch_amax_segments_h16(ls, n, bufs, counts, dtype, out, stream);
+}
+
+int bine_fp8_scales(int n, const uint32_t *amax, int fmt, float *scales, void *stream) {
+  const char *why = nullptr;
+  if (const int rc = fp8_scales_args(n, amax, fmt, scales, &why)) return fp8_refused(__func__, rc, why);
+  return launch_fp8_scales_h16(n, amax, fmt, scales, stream);
+}
+
+int bine_quant_segments(int n, const void *const *src, void *const *dst8, const size_t *counts, int sdtype, int fmt,
+                        const float *scales, void *stream) {
+  const char *why = nullptr;
+  std::vector<QuantLaunch> ls;
+  if (const int rc = quant_args(n, src, dst8, counts, sdtype, fmt, scales, &why, &ls))
+    return fp8_refused(__func__, rc, why);
+  return launch_quant_segments_h16(ls, src, dst8, counts, sdtype, fmt, scales, stream);
+}
+
+int bine_dequant_segments(int n, const void *const *src8, void *const *dst, const size_t *counts, int ddtype,
+                          int fmt, const float *inv_scales, void *stream) {
+  const char *why = nullptr;
+  std::vector<QuantLaunch> ls;
+  if (const int rc = quant_args(n, dst, src8, counts, ddtype, fmt, inv_scales, &why, &ls))
+    return fp8_refused(__func__, rc, why);
+  return launch_dequant_segments_h16(ls, src8, dst, counts, ddtype, fmt, inv_scales, stream);
+}
+
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream) {
   return launch_fill_pico(buf, count, dtype, seed, stream);
 }
@@ -2767,6 +2804,66 @@ int bine_adamw_multi_dyn(bine_comm_t c, int ag_algo, int n, void *const *params,
   return bine_allgather_multi(c, ag_algo, n, nullptr, params, shard_counts, odtype, stream);
 }
 
+// ---- FP8 quantized parameter allgather of a bucket (bine_amd.h) ---------------------------
+
+// the checks that need no communicator: bine_quant_segments' with params8 in
+// dst8's place (a slot may start at any byte), scales, then the in-place
+// allgather's and the amax allreduce's algorithm id.  ls: the launches over src
+// (the body flags are params8's: the caller sets its slots', quant_set_bodies)
+static int quant_multi_args(int amax_algo, int ag_algo, int n, void *const *params8, const void *const *src,
+                            const size_t *shard_counts, int sdtype, int fmt, const float *scales,
+                            const char **why, std::vector<QuantLaunch> *ls = nullptr) {
+  if (const int rc = quant_args(n, src, params8, shard_counts, sdtype, fmt, scales, why, ls)) return rc;
+  if (!scales) {
+    *why = "scales NULL";
+    return BINE_ERR_ARG;
+  }
+  const int rc = shard_args(false, ag_algo, n, nullptr, params8, shard_counts, BINE_UINT8, 0, 1.0, 0);
+  if (rc == BINE_ERR_ARG) {
+    *why = "a shard count above INT_MAX";
+    return rc;
+  }
+  if (rc || amax_algo < BINE_AR_RECURSIVEDOUBLING || amax_algo > BINE_AR_BINE_BLOCK_BY_BLOCK_ANY_EVEN) {
+    *why = "amax_algo outside the allreduce range or ag_algo outside the allgather range";
+    return BINE_ERR_UNSUPPORTED;
+  }
+  return BINE_SUCCESS;
+}
+
+int bine_quant_multi(bine_comm_t c, int amax_algo, int ag_algo, int n, void *const *params8, const void *const *src,
+                     const size_t *shard_counts, int sdtype, int fmt, float *scales, void *stream) {
+  const char *why = nullptr;
+  std::vector<QuantLaunch> qls;  // planned once: the checks' tables serve both kernels
+  if (const int rc =
+          quant_multi_args(amax_algo, ag_algo, n, params8, src, shard_counts, sdtype, fmt, scales, &why, &qls))
+    return fp8_refused(__func__, rc, why);
+  if (!c) return fp8_refused(__func__, BINE_ERR_ARG, "comm NULL");
+  size_t total = 0;
+  for (int k = 0; k < n; k++) total += shard_counts[k];
+  if (total == 0) return BINE_SUCCESS;
+  hipStream_t K = (hipStream_t)stream;
+  // V (n uint32) lives in the multi workspace; fp8_scales has read it before
+  // the allgather below asks for the workspace again
+  char *ws;
+  if (const int rc = multi_workspace(c, ((size_t)n * sizeof(uint32_t) + 255) & ~(size_t)255, K, &ws)) return rc;
+  uint32_t *V = (uint32_t *)ws;
+  std::vector<void *> dst8((size_t)n);
+  for (int k = 0; k < n; k++)
+    dst8[k] = shard_counts[k] ? (char *)params8[k] + (size_t)c->rank * shard_counts[k] : nullptr;
+  quant_set_bodies(qls, src, dst8.data(), sdtype);
+  std::vector<AmaxLaunch> als;
+  for (const QuantLaunch &Q : qls) als.push_back(amax_launch_of(Q));
+  int rc = launch_amax_segments_h16(als, n, src, shard_counts, sdtype, V, K);
+  if (rc) return rc;
+  rc = bine_allreduce(c, amax_algo, BINE_IN_PLACE, V, (size_t)n, BINE_UINT32, BINE_MAX, 0, K);
+  if (rc) return rc;
+  rc = launch_fp8_scales_h16(n, V, fmt, scales, K);
+  if (rc) return rc;
+  rc = launch_quant_segments_h16(qls, src, dst8.data(), shard_counts, sdtype, fmt, scales, K);
+  if (rc) return rc;
+  return bine_allgather_multi(c, ag_algo, n, nullptr, params8, shard_counts, BINE_UINT8, K);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -3117,6 +3214,27 @@ int bine_loopback_run_adamw_multi_dyn(bine_comm_t *comms, int nranks, int ag_alg
     (void)hipSetDevice(comms[r]->device);
     return bine_adamw_multi_dyn(comms[r], ag_algo, n, at(params, r), at(p, r), at(m, r), at(v, r), at(g, r),
                                 at(shard_counts, r), gdtype, odtype, states[r], comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_quant_multi(bine_comm_t *comms, int nranks, int amax_algo, int ag_algo, int n,
+                                  void *const *params8, const void *const *src, const size_t *shard_counts,
+                                  int sdtype, int fmt, float *const *scales, int *statuses) {
+  auto at = [&](auto *list, int r) { return list && n > 0 ? list + (size_t)r * n : list; };
+  // before any thread, stream or HIP call: what a rank would refuse without a communicator
+  const char *why = "scales NULL";
+  int bad = scales ? BINE_SUCCESS : BINE_ERR_ARG;
+  for (int r = 0; !bad && r < nranks; r++)
+    bad = quant_multi_args(amax_algo, ag_algo, n, at(params8, r), at(src, r), shard_counts, sdtype, fmt, scales[r],
+                           &why);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return fp8_refused(__func__, bad, why);
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_quant_multi(comms[r], amax_algo, ag_algo, n, at(params8, r), at(src, r), shard_counts, sdtype, fmt,
+                            scales[r], comms[r]->stream);
   });
 }
 

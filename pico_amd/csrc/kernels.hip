@@ -45,7 +45,9 @@
 // instantiations for the 16-bit floating types (launch_*_h16, reached the
 // same way) and, for those types alone, the wide kernels k_widen / k_narrow /
 // k_reduce_tree_wide (launch_*_h16, called directly: no other compilation
-// holds a wide kernel).  Three translation units compile in parallel.
+// holds a wide kernel), k_adamw_segs and the FP8 kernels k_amax_segs /
+// k_fp8_scales / k_quant_segs, which need the same widen1 / narrow1.  Three
+// translation units compile in parallel.
 //
 // Adding an element type: (1) a case in with_dtype, under the BINE_OPSET of
 // the compilation that is to hold it -- every reduce-family entry point, the
@@ -2319,6 +2321,378 @@ int launch_step_update_h16(void *state, const double *norm2, const bine_step_hyp
   hipLaunchKernelGGL(k_step_update, dim3(1), dim3(1), 0, (hipStream_t)stream, static_cast<StepState *>(state), norm2,
                      *h);
   return status(hipGetLastError());
+}
+
+// ----------------------------------------------------------------------------
+// FP8 quantization of a list of tensors with per-tensor scaling (bine_amd.h):
+// k_amax_segs, k_fp8_scales and k_quant_segs (which also dequantizes).  Both segment
+// kernels take TileTable's dispatch over plan_norm_launches' table of the WIDE
+// side (float, float16 or bfloat16): a tile is kBlock * kScaleU 16-B aligned
+// vectors, and a segment's first workgroup also takes the elements before the
+// first and after the last vector.
+
+// k_amax_segs: the largest magnitude pattern of each tensor.  A workgroup takes
+// kAmaxTilesPerWg consecutive tiles of its segment (amax_launch_of).  A lane
+// keeps the maximum of its elements' patterns without the sign bit IN THE
+// ELEMENT'S OWN FORMAT -- widening is monotone on them, NaNs above infinity
+// included -- and the workgroup's winner is widened once (widen_bits: exact,
+// integer arithmetic, a NaN's payload shifted and not quieted).  Thread 0 then
+// loads out[k], which the launcher zeroed in stream, and issues at most one
+// atomic maximum on it: none where the winner is not above what it loaded.
+template <typename T>
+__device__ __forceinline__ uint32_t mag16(u32x4 v) {
+  if constexpr (sizeof(T) == 4) {
+    v &= 0x7fffffffu;
+  } else {
+    v = __builtin_elementwise_max(v & 0x7fffu, (v >> 16) & 0x7fffu);
+  }
+  const uint32_t a = v.x > v.y ? v.x : v.y, b = v.z > v.w ? v.z : v.w;
+  return a > b ? a : b;
+}
+template <typename T>
+__device__ __forceinline__ uint32_t mag1(T x) {
+  uint_of<T> b;
+  __builtin_memcpy(&b, &x, sizeof b);
+  return (uint32_t)b & (sizeof(T) == 4 ? 0x7fffffffu : 0x7fffu);
+}
+template <typename T>
+__device__ __forceinline__ uint32_t widen_bits(uint32_t m) {
+  if constexpr (std::is_same_v<T, float>) return m;
+  else if constexpr (std::is_same_v<T, BF16>) return m << 16;
+  else {
+    const uint32_t ex = m >> 10, man = m & 0x3ffu;
+    if (ex == 0x1f) return 0x7f800000u | (man << 13);
+    if (ex) return ((ex + 112) << 23) | (man << 13);
+    if (!man) return 0;
+    const int p = 31 - __builtin_clz(man);  // man * 2^-24 with its leading one at bit p
+    return ((uint32_t)(p + 103) << 23) | ((man << (23 - p)) & 0x7fffffu);
+  }
+}
+// the workgroup's maximum of one value per lane; valid in every thread
+__device__ __forceinline__ uint32_t wg_max(uint32_t v, uint32_t *part) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t o = __shfl_xor(v, off, 64);
+    v = o > v ? o : v;
+  }
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint32_t s = part[0];
+#pragma unroll
+  for (int w = 1; w < kBlock / 64; w++) s = part[w] > s ? part[w] : s;
+  return s;
+}
+
+struct AmaxSegs {
+  TileTable<kSegsPerLaunch> tab;
+  uint32_t *out;
+  uint16_t seg[kSegsPerLaunch];  // the caller's tensor per slot
+  NormSeg s[kSegsPerLaunch];
+};
+static_assert(sizeof(AmaxSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_amax_segs(AmaxSegs a) {
+  __shared__ uint32_t part[kBlock / 64];
+  const auto [k, wt] = a.tab.find(blockIdx.x);
+  const uint8_t *p = a.s[k].p;
+  const size_t n = a.s[k].bytes;
+  const size_t head = seg_head((uintptr_t)p, n), nvec = seg_nvec(n, head);
+  uint32_t acc = 0;
+  const u32x4 *vs = reinterpret_cast<const u32x4 *>(p + head);
+  // the workgroup's kAmaxTilesPerWg consecutive tiles, one after another
+#pragma unroll 1
+  for (uint32_t j = 0; j < kAmaxTilesPerWg; j++) {
+    const size_t tile = (size_t)wt * kAmaxTilesPerWg + j;
+    if (tile * kBlock * kScaleU >= nvec) break;  // workgroup-uniform: past the segment's last vector
+    const size_t base = tile * kBlock * kScaleU + threadIdx.x;
+    if (base + (kScaleU - 1) * (size_t)kBlock < nvec) {
+      u32x4 x[kScaleU];
+#pragma unroll
+      for (int u = 0; u < kScaleU; u++) x[u] = vs[base + (size_t)u * kBlock];
+#pragma unroll
+      for (int u = 0; u < kScaleU; u++) {
+        const uint32_t m = mag16<T>(x[u]);
+        acc = m > acc ? m : acc;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < kScaleU; u++) {
+        const size_t i = base + (size_t)u * kBlock;
+        if (i < nvec) {
+          const uint32_t m = mag16<T>(vs[i]);
+          acc = m > acc ? m : acc;
+        }
+      }
+    }
+  }
+  if (wt == 0) {  // head and tail elements of this segment
+    const T *e = reinterpret_cast<const T *>(p);
+    const size_t ne = n / sizeof(T), he = head / sizeof(T), te = (head + nvec * 16) / sizeof(T);
+    for (size_t i = threadIdx.x; i < he; i += kBlock) acc = mag1<T>(e[i]) > acc ? mag1<T>(e[i]) : acc;
+    for (size_t i = te + threadIdx.x; i < ne; i += kBlock) acc = mag1<T>(e[i]) > acc ? mag1<T>(e[i]) : acc;
+  }
+  acc = wg_max(acc, part);
+  if (threadIdx.x == 0 && acc) {
+    // out[k] only grows, so whatever this load sees is at most its current
+    // value: a winner not above it cannot change the maximum and skips the
+    // atomic.  Atomics on one address serialise (8,192 of them on a 256 MiB
+    // tensor doubled the kernel's time); the load costs nothing
+    // measurable (tools/amax_variants.hip).
+    uint32_t *o = a.out + a.seg[k];
+    const uint32_t w = widen_bits<T>(acc);
+    if (w > __hip_atomic_load(o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(o, w);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_amax_zero(int n, uint32_t *out) {
+  const int k = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (k < n) out[k] = 0;
+}
+
+int launch_amax_segments_h16(const std::vector<AmaxLaunch> &ls, int n, const void *const *bufs, const size_t *counts,
+                             int dtype, uint32_t *out, void *stream) {
+  if (n == 0) return BINE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  // the zero fill the atomic maxima start from: a launch of its own, ahead in stream
+  hipLaunchKernelGGL(k_amax_zero, dim3((unsigned)(n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, n, out);
+  if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+  return with_adamw_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    for (const AmaxLaunch &L : ls) {
+      AmaxSegs a;
+      a.out = out;
+      fill_segs(a, L, [&](int s) {
+        return NormSeg{(uint8_t *)const_cast<void *>(bufs[L.seg[s]]), (uint64_t)(counts[L.seg[s]] * sizeof(T))};
+      });
+      for (int s = 0; s < kSegsPerLaunch; s++) a.seg[s] = s < L.nseg ? (uint16_t)L.seg[s] : 0;
+      hipLaunchKernelGGL((k_amax_segs<T>), dim3(L.tile0[L.nseg]), dim3(kBlock), 0, st, a);
+      if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+    }
+    return BINE_SUCCESS;
+  });
+}
+
+// k_fp8_scales: thread k runs fp8_scale_rule (bine_internal.h) -- the statement
+// the host twin compiles -- on amax[k]
+__global__ __launch_bounds__(kBlock) void k_fp8_scales(int n, const uint32_t *amax, int fmt, float *scales) {
+  const int k = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (k < n) fp8_scale_rule(amax[k], fmt, scales + k, scales + n + k);
+}
+
+int launch_fp8_scales_h16(int n, const uint32_t *amax, int fmt, float *scales, void *stream) {
+  if (n == 0) return BINE_SUCCESS;
+  hipLaunchKernelGGL(k_fp8_scales, dim3((unsigned)(n + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, n,
+                     amax, fmt, scales);
+  return status(hipGetLastError());
+}
+
+// Four binary32 values as four FP8 bytes, element 0 lowest.  A NaN becomes
+// 0x7F by its own select (the conversion sees 0.0 in its place, byte 0x00,
+// and the select ORs the NaN byte in); everything else is clamped to +-FMAX,
+// so the packed conversion never sees a value past the format's range and
+// only has to round: nearest even, the format's subnormals kept, -0 kept.
+template <int FMT>
+__device__ __forceinline__ uint32_t quant4(float y0, float y1, float y2, float y3) {
+  constexpr float kMax = FMT == BINE_FP8_E4M3 ? 448.0f : 57344.0f;
+  uint32_t nan = 0;
+  auto prep = [&](float y, int sh) {
+    if (y != y) {
+      nan |= 0x7fu << sh;
+      return 0.0f;
+    }
+    return fminf(fmaxf(y, -kMax), kMax);
+  };
+  const float c0 = prep(y0, 0), c1 = prep(y1, 8), c2 = prep(y2, 16), c3 = prep(y3, 24);
+  int w = 0;
+  if constexpr (FMT == BINE_FP8_E4M3) {
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(c0, c1, w, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(c2, c3, w, true);
+  } else {
+    w = __builtin_amdgcn_cvt_pk_bf8_f32(c0, c1, w, false);
+    w = __builtin_amdgcn_cvt_pk_bf8_f32(c2, c3, w, true);
+  }
+  return (uint32_t)w | nan;
+}
+template <typename T, int FMT>
+__device__ __forceinline__ uint8_t quant1(T x, float s) {
+  return (uint8_t)quant4<FMT>(adamw_widen<T>(x) * s, 0.0f, 0.0f, 0.0f);
+}
+// the bytes of one 16-B source vector: one word for float, two for the 16-bit types
+template <typename T>
+using q8_of = std::conditional_t<sizeof(T) == 4, uint32_t, u32x2>;
+template <typename T, int FMT>
+__device__ __forceinline__ q8_of<T> quant16(u32x4 v, float s) {
+  if constexpr (sizeof(T) == 4) {
+    float f[4];
+    __builtin_memcpy(f, &v, 16);
+    return quant4<FMT>(f[0] * s, f[1] * s, f[2] * s, f[3] * s);
+  } else {
+    const W8 w = widen16<T>(v);
+    u32x2 r;
+    r.x = quant4<FMT>(w.a.x * s, w.a.y * s, w.a.z * s, w.a.w * s);
+    r.y = quant4<FMT>(w.b.x * s, w.b.y * s, w.b.z * s, w.b.w * s);
+    return r;
+  }
+}
+
+// the non-NaN byte b as the binary32 pattern of its value, exactly
+template <int FMT>
+__device__ __forceinline__ uint32_t fp8_decode_bits(uint32_t b) {
+  constexpr int MB = FMT == BINE_FP8_E4M3 ? 3 : 2, bias = FMT == BINE_FP8_E4M3 ? 7 : 15;
+  const uint32_t mag = b & 0x7fu, sgn = (b & 0x80u) << 24;
+  if (FMT == BINE_FP8_E5M2 && mag == 0x7cu) return sgn | 0x7f800000u;
+  if (mag >> MB) return sgn | ((mag << (23 - MB)) + ((uint32_t)(127 - bias) << 23));  // exponent and fraction, rebased
+  const float f = (float)mag * (FMT == BINE_FP8_E4M3 ? 0x1p-9f : 0x1p-16f);  // subnormal: mag * 2^(1 - bias - MB)
+  uint32_t r;
+  __builtin_memcpy(&r, &f, 4);
+  return sgn | r;
+}
+// byte b as an element of T (its pattern): narrow(decode(b) * inv); a NaN byte
+// gives T's quiet NaN with the byte's sign
+template <typename T, int FMT>
+__device__ __forceinline__ uint_of<T> dequant1(uint32_t b, float inv) {
+  const bool nan = FMT == BINE_FP8_E4M3 ? (b & 0x7fu) == 0x7fu : (b & 0x7fu) > 0x7cu;
+  if (nan) {
+    const uint32_t q = ((b & 0x80u) << 24) | 0x7fc00000u;
+    if constexpr (std::is_same_v<T, float>) return q;
+    else if constexpr (std::is_same_v<T, BF16>) return (uint16_t)(q >> 16);
+    else return (uint16_t)(((b & 0x80u) << 8) | 0x7e00u);
+  }
+  const uint32_t d = fp8_decode_bits<FMT>(b);
+  float f;
+  __builtin_memcpy(&f, &d, 4);
+  const T t = adamw_narrow<T>(f * inv);
+  uint_of<T> r;
+  __builtin_memcpy(&r, &t, sizeof r);
+  return r;
+}
+template <typename T, int FMT>
+__device__ __forceinline__ u32x4 dequant16(q8_of<T> b, float inv) {
+  constexpr int V = 16 / (int)sizeof(T);
+  uint32_t w[V / 4];
+  __builtin_memcpy(w, &b, sizeof w);
+  uint_of<T> e[V];
+#pragma unroll
+  for (int j = 0; j < V; j++) e[j] = dequant1<T, FMT>((w[j / 4] >> (8 * (j % 4))) & 0xffu, inv);
+  u32x4 r;
+  __builtin_memcpy(&r, e, 16);
+  return r;
+}
+
+// One descriptor per slot: the wide buffer, the FP8 bytes, the element count.
+// A slot whose byte side stands on a V-byte boundary wherever the wide side
+// stands on a 16-B one (V = 16 / sizeof(T)) takes the vector body -- a lane
+// handles one wide vector and its V bytes per access, all loads of a full tile
+// issued before the first use, non-temporal loads of a full tile (the source is
+// read last here) and non-temporal stores on every path; any other slot takes the element body (QuantSegs::elem,
+// set by the host): the same operations through element and byte accesses.
+struct QuantSeg {
+  uint8_t *wide, *b8;
+  uint64_t n;  // elements
+};
+struct QuantSegs {
+  TileTable<kSegsPerLaunch> tab;
+  uint64_t elem[(kSegsPerLaunch + 63) / 64];  // bit s: slot s takes the element body
+  const float *scales;                        // per tensor; NULL: 1
+  uint16_t seg[kSegsPerLaunch];               // the caller's tensor per slot
+  QuantSeg s[kSegsPerLaunch];
+};
+static_assert(sizeof(QuantSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+
+// DEQ false: b8 = encode(wide * scale); true: wide = narrow(decode(b8) * scale)
+template <typename T, int FMT, bool DEQ>
+__global__ __launch_bounds__(kBlock) void k_quant_segs(QuantSegs a) {
+  constexpr size_t V = 16 / sizeof(T);
+  using BV = q8_of<T>;
+  const auto [k, wt] = a.tab.find(blockIdx.x);
+  T *wide = reinterpret_cast<T *>(a.s[k].wide);
+  uint8_t *b8 = a.s[k].b8;
+  const size_t n = a.s[k].n;
+  // the split in elements: wide is aligned to its element, so the head is whole elements
+  const size_t he = seg_head((uintptr_t)wide, sizeof(T) * n) / sizeof(T), nvec = (n - he) / V;
+  const bool elem = (a.elem[k >> 6] >> (k & 63)) & 1;
+  u32x4 *vw = reinterpret_cast<u32x4 *>(wide + he);
+  BV *vb = reinterpret_cast<BV *>(b8 + he);
+  const size_t base = (size_t)wt * kBlock * kScaleU + threadIdx.x;
+  const bool full = !elem && ((size_t)wt + 1) * kBlock * kScaleU <= nvec;  // workgroup-uniform
+  [[maybe_unused]] u32x4 xw[kScaleU];
+  [[maybe_unused]] BV xb[kScaleU];
+  if (full) {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if constexpr (DEQ) xb[u] = __builtin_nontemporal_load(vb + i);
+      else xw[u] = __builtin_nontemporal_load(vw + i);
+    }
+  }
+  const float s = a.scales ? a.scales[a.seg[k]] : 1.0f;
+  auto one = [&](size_t i) {
+    if constexpr (DEQ) {
+      __builtin_nontemporal_store(dequant1<T, FMT>(b8[i], s), reinterpret_cast<uint_of<T> *>(wide) + i);
+    } else {
+      __builtin_nontemporal_store(quant1<T, FMT>(wide[i], s), b8 + i);
+    }
+  };
+  if (wt == 0) {  // head and tail elements of this segment
+    for (size_t i = threadIdx.x; i < he; i += kBlock) one(i);
+    for (size_t i = he + nvec * V + threadIdx.x; i < n; i += kBlock) one(i);
+  }
+  if (full) {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if constexpr (DEQ) __builtin_nontemporal_store(dequant16<T, FMT>(xb[u], s), vw + i);
+      else __builtin_nontemporal_store(quant16<T, FMT>(xw[u], s), vb + i);
+    }
+  } else if (!elem) {
+#pragma unroll
+    for (int u = 0; u < kScaleU; u++) {
+      const size_t i = base + (size_t)u * kBlock;
+      if (i < nvec) {
+        if constexpr (DEQ) __builtin_nontemporal_store(dequant16<T, FMT>(vb[i], s), vw + i);
+        else __builtin_nontemporal_store(quant16<T, FMT>(vw[i], s), vb + i);
+      }
+    }
+  } else {  // the tile's elements one by one
+    const size_t lo = he + (size_t)wt * kBlock * kScaleU * V, end = he + nvec * V;
+    const size_t hi = lo + (size_t)kBlock * kScaleU * V < end ? lo + (size_t)kBlock * kScaleU * V : end;
+    for (size_t i = lo + threadIdx.x; i < hi; i += kBlock) one(i);
+  }
+}
+
+template <bool DEQ>
+static int quant_issue(const std::vector<QuantLaunch> &ls, const void *const *wide, const void *const *b8,
+                       const size_t *counts, int dtype, int fmt, const float *scales, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  return with_adamw_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    for (const QuantLaunch &L : ls) {
+      QuantSegs a;
+      a.scales = scales;
+      for (size_t w = 0; w < sizeof a.elem / sizeof a.elem[0]; w++) a.elem[w] = L.elem[w];
+      fill_segs(a, L, [&](int s) {
+        const int k = L.seg[s];
+        return QuantSeg{(uint8_t *)const_cast<void *>(wide[k]), (uint8_t *)const_cast<void *>(b8[k]),
+                        (uint64_t)counts[k]};
+      });
+      for (int s = 0; s < kSegsPerLaunch; s++) a.seg[s] = s < L.nseg ? (uint16_t)L.seg[s] : 0;
+      const dim3 grid(L.tile0[L.nseg]), blk(kBlock);
+      if (fmt == BINE_FP8_E4M3) hipLaunchKernelGGL((k_quant_segs<T, BINE_FP8_E4M3, DEQ>), grid, blk, 0, st, a);
+      else hipLaunchKernelGGL((k_quant_segs<T, BINE_FP8_E5M2, DEQ>), grid, blk, 0, st, a);
+      if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+    }
+    return BINE_SUCCESS;
+  });
+}
+
+int launch_quant_segments_h16(const std::vector<QuantLaunch> &ls, const void *const *src, void *const *dst8,
+                              const size_t *counts, int sdtype, int fmt, const float *scales, void *stream) {
+  return quant_issue<false>(ls, src, dst8, counts, sdtype, fmt, scales, stream);
+}
+
+int launch_dequant_segments_h16(const std::vector<QuantLaunch> &ls, const void *const *src8, void *const *dst,
+                                const size_t *counts, int ddtype, int fmt, const float *inv_scales, void *stream) {
+  return quant_issue<true>(ls, dst, src8, counts, ddtype, fmt, inv_scales, stream);
 }
 #endif  // BINE_OPSET == 2
 

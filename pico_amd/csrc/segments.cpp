@@ -13,6 +13,11 @@
 //   plan_adamw_launches / bine_plan_adamw    k_adamw_segs: plan_norm_launches' table over p, cut at
 //                                            kAdamwSegsPerLaunch descriptors, with the step's constants
 //                                            (bine_adamw_consts) beside them (tools/adamw_check.cpp)
+//   plan_quant_launches / bine_plan_quant    k_quant_segs (both directions): plan_norm_launches' table over
+//                                            the wide side with one body flag per slot; the FP8 calls'
+//                                            refusals (amax_args, fp8_scales_args, quant_args) and
+//                                            bine_fp8_scale_host, the host compilation of fp8_scale_rule
+//                                            (tools/quant_check.cpp)
 // Dynamic loss scaling keeps its host half here too:
 // bine_step_state_init, the refusals (step_update_args, adamw_dyn_args) and
 // bine_step_update_host, the host compilation of the statement k_step_update
@@ -216,7 +221,124 @@ int step_update_args(const void *state, const void *norm2, const bine_step_hyper
   return BINE_SUCCESS;
 }
 
+int plan_quant_launches(int n, const uint64_t *wide, const uint64_t *bytes8, const size_t *counts, int dtype,
+                        std::vector<QuantLaunch> &out) {
+  out.clear();
+  const size_t esz = adamw_esz(dtype);
+  if (!esz) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX) return BINE_ERR_ARG;
+  if (n > 0 && (!wide || !bytes8 || !counts)) return BINE_ERR_ARG;
+  for (int k = 0; k < n; k++)
+    if (counts[k] && (!wide[k] || !bytes8[k])) return BINE_ERR_ARG;
+  std::vector<SegLaunch> ls;
+  if (const int rc = plan_norm_launches(n, wide, counts, dtype, ls, nullptr)) return rc;
+  for (const SegLaunch &L : ls) {
+    out.emplace_back();
+    static_cast<LaunchTable<kSegsPerLaunch> &>(out.back()) = L;
+  }
+  for (QuantLaunch &Q : out)
+    for (int s = 0; s < Q.nseg; s++) {
+      const int k = Q.seg[s];
+      // h: the elements before wide's first 16-B boundary (the addresses' flag,
+      // whatever the count); there bytes8 must stand on a boundary of the 16 / esz
+      // bytes one wide vector holds
+      const uint64_t h = seg_head(wide[k], 16) / esz;
+      if ((bytes8[k] + h) % (16 / esz)) Q.elem[s >> 6] |= (uint64_t)1 << (s & 63);
+    }
+  return BINE_SUCCESS;
+}
+
+void quant_set_bodies(std::vector<QuantLaunch> &ls, const void *const *wide, const void *const *bytes8, int dtype) {
+  const size_t esz = adamw_esz(dtype);
+  for (QuantLaunch &Q : ls) {
+    for (uint64_t &w : Q.elem) w = 0;
+    for (int s = 0; s < Q.nseg; s++) {
+      const int k = Q.seg[s];
+      const uint64_t h = seg_head((uint64_t)(uintptr_t)wide[k], 16) / esz;
+      if (((uint64_t)(uintptr_t)bytes8[k] + h) % (16 / esz)) Q.elem[s >> 6] |= (uint64_t)1 << (s & 63);
+    }
+  }
+}
+
+AmaxLaunch amax_launch_of(const LaunchTable<kSegsPerLaunch> &tiles) {
+  AmaxLaunch A = tiles;
+  uint32_t wgs = 0;
+  for (int s = 0; s < tiles.nseg; s++) {
+    A.tile0[s] = wgs;
+    wgs += (tiles.tile0[s + 1] - tiles.tile0[s] + kAmaxTilesPerWg - 1) / kAmaxTilesPerWg;
+  }
+  A.tile0[tiles.nseg] = wgs;
+  return A;
+}
+
+static int refuse(const char **why, const char *what) {
+  if (why) *why = what;
+  return BINE_ERR_ARG;
+}
+
+int amax_args(int n, const void *const *bufs, const size_t *counts, int dtype, const void *out, const char **why,
+              std::vector<AmaxLaunch> *ls) {
+  if (!adamw_esz(dtype)) return refuse(why, "dtype: float, float16 or bfloat16");
+  std::vector<uint64_t> a;
+  if (seg_list_addrs(n, counts, {bufs}, a)) return refuse(why, "n outside [0, BINE_MULTI_MAX], or a NULL array");
+  std::vector<SegLaunch> tiles;
+  if (plan_norm_launches(n, a.data(), counts, dtype, tiles, nullptr))
+    return refuse(why, "a NULL buffer with a non-zero count, or a buffer not aligned to its element");
+  if (!out || ((uintptr_t)out & 3)) return refuse(why, "out NULL or not 4-byte aligned");
+  if (ls) {
+    ls->clear();
+    for (const SegLaunch &L : tiles) ls->push_back(amax_launch_of(L));
+  }
+  return BINE_SUCCESS;
+}
+
+int fp8_scales_args(int n, const void *amax, int fmt, const void *scales, const char **why) {
+  if (!fp8_fmt_ok(fmt)) return refuse(why, "fmt: BINE_FP8_E4M3 or BINE_FP8_E5M2");
+  if (n < 0 || n > BINE_MULTI_MAX) return refuse(why, "n outside [0, BINE_MULTI_MAX]");
+  if (!amax || ((uintptr_t)amax & 3)) return refuse(why, "amax NULL or not 4-byte aligned");
+  if (!scales || ((uintptr_t)scales & 3)) return refuse(why, "scales NULL or not 4-byte aligned");
+  return BINE_SUCCESS;
+}
+
+int quant_args(int n, const void *const *wide, const void *const *bytes8, const size_t *counts, int dtype, int fmt,
+               const void *scales, const char **why, std::vector<QuantLaunch> *ls) {
+  if (!adamw_esz(dtype)) return refuse(why, "dtype: float, float16 or bfloat16");
+  if (!fp8_fmt_ok(fmt)) return refuse(why, "fmt: BINE_FP8_E4M3 or BINE_FP8_E5M2");
+  std::vector<uint64_t> a;  // wide, bytes8
+  if (seg_list_addrs(n, counts, {wide, bytes8}, a))
+    return refuse(why, "n outside [0, BINE_MULTI_MAX], or a NULL array");
+  std::vector<QuantLaunch> local;
+  if (plan_quant_launches(n, a.data(), a.data() + n, counts, dtype, ls ? *ls : local))
+    return refuse(why, "a NULL buffer with a non-zero count, or a wide buffer not aligned to its element");
+  if ((uintptr_t)scales & 3) return refuse(why, "scales not 4-byte aligned");
+  return BINE_SUCCESS;
+}
+
 }  // namespace bine
+
+extern "C" int bine_fp8_scale_host(uint32_t amax_bits, int fmt, float *scale, float *inv) {
+  if (!bine::fp8_fmt_ok(fmt) || !scale || !inv) return BINE_ERR_ARG;
+  bine::fp8_scale_rule(amax_bits, fmt, scale, inv);
+  return BINE_SUCCESS;
+}
+
+extern "C" int64_t bine_plan_quant(int n, const uint64_t *wide, const uint64_t *bytes8, const size_t *counts,
+                                   int dtype, uint64_t *out, int64_t cap) {
+  std::vector<bine::QuantLaunch> ls;
+  const int rc = bine::plan_quant_launches(n, wide, bytes8, counts, dtype, ls);
+  if (rc) return -(int64_t)rc;
+  int64_t nt = 0;
+  for (size_t l = 0; l < ls.size(); l++) {
+    const bine::QuantLaunch &Q = ls[l];
+    for (int s = 0; s < Q.nseg; s++, nt++)
+      if (out && nt < cap) {
+        uint64_t *e = out + 5 * nt;
+        e[0] = l, e[1] = (uint64_t)Q.seg[s], e[2] = Q.tile0[s], e[3] = Q.tile0[s + 1] - Q.tile0[s];
+        e[4] = (Q.elem[s >> 6] >> (s & 63)) & 1;
+      }
+  }
+  return nt;
+}
 
 extern "C" int bine_step_state_init(void *host_state, double scale, int64_t step, double beta1, double beta2) {
   if (!host_state || ((uintptr_t)host_state & 7)) return BINE_ERR_ARG;
