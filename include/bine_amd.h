@@ -680,6 +680,93 @@ int bine_dequant_segments(int n, const void *const *src8, void *const *dst, cons
                           int fmt, const float *inv_scales, void *stream);
 int64_t bine_plan_quant(int n, const uint64_t *wide, const uint64_t *bytes8, const size_t *counts, int dtype,
                         uint64_t *out, int64_t cap);
+/* ---- MX block-scaled quantization of a list of tensors (OCP MX v1.0) -------------
+ * Blocks of 32 elements share one E8M0 scale byte: what gfx950's block-scaled
+ * matrix instructions take.  A block's scale depends on its own 32 elements
+ * alone, so the quantization is one pass without atomics, without a reduction
+ * across workgroups or ranks and without workspace; bine_mx_quant_multi (below,
+ * with the collectives) does it for a sharded bucket and gathers the bytes.
+ * Formats (fmt): BINE_MX_E4M3 and BINE_MX_E5M2, the encodings of
+ * bine_fp8_format_t with the same values, and BINE_MX_E2M1, OCP FP4: 1 sign
+ * bit, 2 exponent bits, 1 fraction bit, bias 1, magnitudes 0, 0.5, 1, 1.5, 2,
+ * 3, 4, 6, no infinity and no NaN, two per byte with element 2j in the LOW
+ * nibble of byte j.  emax = 8 / 15 / 2, FMAX = 448 / 57344 / 6.  Wide types
+ * and widen() as above.  dbytes(c) = c for the FP8 formats, ceil(c / 2) for
+ * E2M1.
+ *
+ * Block b of a segment is its elements [32b, min(32b + 32, count)), counted
+ * from the segment's first element whatever its address; the last block may
+ * be short; nblk = ceil(count / 32).
+ *
+ * The scale byte S of a block (bine_mx_scale_host, and the kernel: ONE inline
+ * function compiled for both, mx_scale_rule in pico_amd/csrc/bine_internal.h),
+ * integer arithmetic on the pattern:
+ *   A = max over the block of bits(widen(x)) & 0x7fffffff, as unsigned
+ *   A >= 0x7f800000 (an inf or a NaN in the block):  S = 0xFF
+ *   A == 0:                                          S = 0
+ *   else  E = floor(log2 |max|): (A >> 23) - 127 for a normal pattern,
+ *             p - 149 for a subnormal one (p = its leading one's bit)
+ *         S = max(E - emax + 127, 0)                 (never above 252)
+ * bine_mx_scale_host(amax_bits = A, fmt, s): BINE_ERR_ARG for fmt or s NULL.
+ *
+ * bine_mx_quant_segments: dst8[k] receives dbytes(counts[k]) data bytes and
+ * scl8[k] nblk scale bytes, both at any byte alignment.  Per block: S by the
+ * rule; with S = 0xFF every data byte (nibble) of the block is 0; otherwise
+ * per element
+ *   y = widen(x) * 2^(127 - S)   exact wherever |y| >= 2^-126; below that every
+ *                                format encodes y as zero
+ *   y = min(max(y, -FMAX), FMAX) the block's maximum lies in [2^emax,
+ *                                2^(emax+1)), so the clamp does act: 500 gives
+ *                                448 in E4M3
+ *   y rounded to nearest even into the format, its subnormals kept and the
+ *   sign of zero kept
+ * A short last block of E2M1 with an odd count leaves the last byte's high
+ * nibble 0.  Sources are not written; ranges must not overlap (not checked).
+ * Mechanism: k_mx_segs over a tile table of the SOURCE -- tiles of 32 KiB
+ * counted from the segment's first element (8,192 floats or 16,384 16-bit
+ * elements: whole blocks), at least one workgroup per non-empty segment,
+ * BINE_MX_SEGS_PER_LAUNCH descriptors (three pointers and a count) per launch
+ * by value.  A segment whose source is 16-B aligned and whose dst8 is aligned
+ * to the bytes one source vector yields (4 / 8 for FP8 from float / 16-bit, 2
+ * / 4 for E2M1) takes the vector body: a lane loads one 16-B vector per step,
+ * all loads of a full tile issued before the first use, the 8 (float) or 4
+ * (16-bit) adjacent lanes that hold a block agree on A by cross-lane integer
+ * maxima, every lane encodes its own elements and stores its 2-, 4- or 8-byte
+ * word, one lane of the group stores the scale byte; every access of a full
+ * tile is non-temporal.  The segment's final short block, and every other
+ * segment, takes the element body: one element per lane, 32 lanes a block,
+ * byte stores, the same bits.  BINE_ERR_ARG, before any HIP call, in this
+ * order: sdtype or fmt; n < 0 or n > BINE_MULTI_MAX; src, dst8, scl8 or counts
+ * NULL with n > 0; a NULL buffer with a non-zero count; a source not aligned
+ * to its element size.
+ *
+ * bine_mx_dequant_segments: the inverse.  S = 0xFF gives the destination
+ * type's positive quiet NaN (0x7fc00000 / 0x7e00 / 0x7fc0) for every element
+ * of the block; otherwise dst = narrow(decode(b) * 2^(S - 127)): decode exact,
+ * one binary32 multiplication (at S = 0 by the subnormal 2^-127; subnormals
+ * kept, overflow to infinity IEEE's), one rounding for the 16-bit types.  An
+ * E4M3 or E5M2 NaN byte gives the quiet NaN with the byte's sign, an E5M2
+ * infinity byte +-inf.  Arbitrary input bytes are legal.  The tile table is
+ * the DESTINATION's; bodies and refusals as bine_mx_quant_segments with the
+ * roles swapped (the same kernel, k_mx_segs' dequantizing form).
+ *
+ * bine_plan_mx (host only): the launches bine_mx_quant_segments issues for
+ * these addresses (bine_mx_dequant_segments: pass dst as `wide`).  Returns the
+ * number of non-empty segments (may exceed cap) or -status; with `out`, one
+ * record of 5 uint64 per non-empty segment, in launch order: (launch, segment,
+ * its first workgroup in the launch, its workgroups, body: 0 vector / 1
+ * element).
+ * Not provided: MXFP6, the swizzled scale layout a particular GEMM wants
+ * (scales are linear, in block order). */
+typedef enum { BINE_MX_E4M3 = 0, BINE_MX_E5M2 = 1, BINE_MX_E2M1 = 2 } bine_mx_format_t;
+#define BINE_MX_SEGS_PER_LAUNCH 112
+int bine_mx_scale_host(uint32_t amax_bits, int fmt, uint8_t *s);
+int bine_mx_quant_segments(int n, const void *const *src, void *const *dst8, void *const *scl8,
+                           const size_t *counts, int sdtype, int fmt, void *stream);
+int bine_mx_dequant_segments(int n, const void *const *src8, const void *const *scl8, void *const *dst,
+                             const size_t *counts, int ddtype, int fmt, void *stream);
+int64_t bine_plan_mx(int n, const uint64_t *wide, const uint64_t *data8, const uint64_t *scl8, const size_t *counts,
+                     int dtype, int fmt, uint64_t *out, int64_t cap);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -1187,11 +1274,38 @@ int bine_adamw_multi_dyn(bine_comm_t comm, int ag_algo, int n, void *const *para
  * allreduce range or ag_algo outside the allgather range
  * (BINE_ERR_UNSUPPORTED); comm == NULL (BINE_ERR_ARG).  Steps 2 and 5 return
  * whatever the single calls refuse.  Not provided: delayed scaling (the store
- * fused into k_adamw_segs), amax histories, block or MX scaling, FP8 gradients
- * in the reduce-scatter. */
+ * fused into k_adamw_segs), amax histories, FP8 gradients in the
+ * reduce-scatter. */
 int bine_quant_multi(bine_comm_t comm, int amax_algo, int ag_algo, int n, void *const *params8,
                      const void *const *src, const size_t *shard_counts, int sdtype, int fmt, float *scales,
                      void *stream);
+/* ---- MX block-scaled parameter allgather of a bucket ------------------------------
+ * bine_quant_multi's block-scaled form: params8[k] is the full tensor's data
+ * bytes, comm size * dbytes(shard_counts[k]); scales8[k] its comm size *
+ * shard_counts[k] / 32 scale bytes; src[k] this rank's shard (shard_counts[k]
+ * elements of sdtype).  The exchange carries 1 + 1/32 bytes per element (FP8)
+ * or 1/2 + 1/32 (E2M1).  Bit for bit this sequence, all on the caller's stream:
+ *   1. bine_mx_quant_segments(n, src, dst8, scl8, shard_counts, sdtype, fmt) with
+ *      dst8[k] = params8[k] + rank * dbytes(shard_counts[k]) and scl8[k] =
+ *      scales8[k] + rank * shard_counts[k] / 32: this rank's slots;
+ *   2. ONE bine_allgather_multi(comm, ag_algo, 2n, NULL (in place), {params8...,
+ *      scales8...}, {dbytes(shard_counts)..., shard_counts / 32...}, BINE_UINT8).
+ * No allreduce and no workspace of its own.  Every shard count must be a
+ * multiple of 32: a tensor's blocks then never straddle ranks (the gathered
+ * bytes are what bine_mx_quant_segments gives on the whole tensor) and E2M1
+ * bytes stay whole.  The kernel of 1 is an ordinary launch, never captured;
+ * with graph mode on the allgather replays as any call on those addresses.
+ * With n = 0 or every shard count 0 the call succeeds and writes nothing.
+ * Refusals, before any exchange and any HIP call, in this order: sdtype or
+ * fmt; n < 0 or n > BINE_MULTI_MAX / 2; params8, scales8, src or shard_counts
+ * NULL with n > 0; a NULL buffer with a non-zero count; a source not aligned
+ * to its element size; a shard count not a multiple of 32, or above INT_MAX
+ * (all BINE_ERR_ARG); ag_algo outside the allgather range
+ * (BINE_ERR_UNSUPPORTED); comm == NULL (BINE_ERR_ARG).  Step 2 returns whatever
+ * the single call refuses.  Not provided: MX gradients in the reduce-scatter,
+ * the store fused into k_adamw_segs. */
+int bine_mx_quant_multi(bine_comm_t comm, int ag_algo, int n, void *const *params8, void *const *scales8,
+                        const void *const *src, const size_t *shard_counts, int sdtype, int fmt, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -1306,6 +1420,12 @@ int bine_loopback_run_adamw_multi_dyn(bine_comm_t *comms, int nranks, int ag_alg
 int bine_loopback_run_quant_multi(bine_comm_t *comms, int nranks, int amax_algo, int ag_algo, int n,
                                   void *const *params8, const void *const *src, const size_t *shard_counts,
                                   int sdtype, int fmt, float *const *scales, int *statuses);
+/* bine_mx_quant_multi on every virtual rank: params8, scales8 and src hold
+ * nranks * n entries, rank r's tensor k at [r * n + k]; shard_counts n entries
+ * (every rank's) */
+int bine_loopback_run_mx_quant_multi(bine_comm_t *comms, int nranks, int ag_algo, int n, void *const *params8,
+                                     void *const *scales8, const void *const *src, const size_t *shard_counts,
+                                     int sdtype, int fmt, int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

@@ -83,6 +83,10 @@ class OpTime(ctypes.Structure):
 # bine_fp8_format_t: the OCP FP8 encodings of bine_quant_segments, and their largest finite values
 FP8_FORMATS = {"e4m3": 0, "e5m2": 1}
 FP8_MAX = {"e4m3": 448.0, "e5m2": 57344.0}
+# bine_mx_format_t: the element formats of the MX calls (32 elements per E8M0 scale byte), and their emax
+MX_FORMATS = {"e4m3": 0, "e5m2": 1, "e2m1": 2}
+MX_EMAX = {"e4m3": 8, "e5m2": 15, "e2m1": 2}
+MX_SEGS_PER_LAUNCH = 112
 
 
 # the step state of bine_step_update (BINE_STEP_STATE_BYTES: 8 doubles, 8 floats)
@@ -227,6 +231,12 @@ def lib():
         "bine_plan_quant": ([i, vp, vp, vp, i, vp, ctypes.c_int64], ctypes.c_int64),
         "bine_quant_multi": ([vp, i, i, i, vp, vp, vp, i, i, vp, vp], i),
         "bine_loopback_run_quant_multi": ([vp, i, i, i, i, vp, vp, vp, i, i, vp, vp], i),
+        "bine_mx_scale_host": ([u32, i, ctypes.POINTER(ctypes.c_uint8)], i),
+        "bine_mx_quant_segments": ([i, vp, vp, vp, vp, i, i, vp], i),
+        "bine_mx_dequant_segments": ([i, vp, vp, vp, vp, i, i, vp], i),
+        "bine_plan_mx": ([i, vp, vp, vp, vp, i, i, vp, ctypes.c_int64], ctypes.c_int64),
+        "bine_mx_quant_multi": ([vp, i, i, vp, vp, vp, vp, i, i, vp], i),
+        "bine_loopback_run_mx_quant_multi": ([vp, i, i, i, vp, vp, vp, vp, i, i, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

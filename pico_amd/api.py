@@ -1189,6 +1189,108 @@ def loopback_quant_multi(comms, amax_algo, ag_algo, params8, src, fmt, scales, s
     return rc, list(st)
 
 
+# ---- MX block-scaled quantization of a bucket (32 elements per E8M0 scale byte) -------------
+
+def _mx(fmt) -> int:
+    return fmt if isinstance(fmt, int) else _lib.MX_FORMATS[fmt]
+
+
+def mx_dbytes(count: int, fmt) -> int:
+    """The data bytes of `count` elements: one each, two per byte for "e2m1"."""
+    return (count + 1) // 2 if _mx(fmt) == _lib.MX_FORMATS["e2m1"] else count
+
+
+def mx_scale_host(amax_bits: int, fmt) -> int:
+    """The E8M0 scale byte of a block whose largest bits(x) & 0x7fffffff is
+    amax_bits (bine_mx_scale_host, host only): 0xFF for an inf or a NaN, 0 for
+    an all-zero block, else max(floor(log2 amax) - emax + 127, 0) with emax 8
+    ("e4m3"), 15 ("e5m2") or 2 ("e2m1")."""
+    s = ctypes.c_uint8()
+    check(lib().bine_mx_scale_host(int(amax_bits) & 0xFFFFFFFF, _mx(fmt), ctypes.byref(s)), "bine_mx_scale_host")
+    return s.value
+
+
+def plan_mx(wide: Sequence[int], data8: Sequence[int], scl8: Sequence[int], counts: Sequence[int], dtype, fmt):
+    """The launches of mx_quant_segments for these source (`wide`), data and
+    scale addresses -- of mx_dequant_segments with the destination as `wide` --
+    (bine_plan_mx, host only): a list of (launch, segment, first workgroup in
+    the launch, workgroups, body) per non-empty segment, body 0 = vector,
+    1 = element."""
+    n = len(counts)
+    if len(wide) != n or len(data8) != n or len(scl8) != n:
+        raise ValueError("plan_mx: the address lists and counts differ in length")
+    arr = lambda a: (ctypes.c_uint64 * max(n, 1))(*a)  # noqa: E731
+    args = (n, arr(wide), arr(data8), arr(scl8), (ctypes.c_size_t * max(n, 1))(*counts), _adamw_dtype(dtype, ()),
+            _mx(fmt))
+    cap = lib().bine_plan_mx(*args, None, 0)
+    if cap < 0:
+        raise BineError(int(-cap), "bine_plan_mx")
+    out = (ctypes.c_uint64 * (5 * max(cap, 1)))()
+    lib().bine_plan_mx(*args, out, cap)
+    return [tuple(out[5 * t:5 * t + 5]) for t in range(cap)]
+
+
+def mx_quant_segments(src, dst8, scl8, fmt, sdtype=None, counts=None, stream=None) -> None:
+    """Tensor src[k] as OCP MX blocks (bine_mx_quant_segments): every 32
+    elements, counted from the tensor's first, share the scale byte scl8[k][b]
+    = mx_scale_host of the block's largest magnitude, and dst8[k] holds
+    widen(x) * 2^(127 - S) clamped to +-FMAX and rounded to nearest even into
+    "e4m3" / "e5m2" (one byte each) or "e2m1" (two per byte, the even element
+    in the low nibble).  A block with an inf or a NaN gets S = 0xFF and zero
+    data.  src float / float16 / bfloat16; dst8 and scl8 uint8 at any byte
+    alignment, mx_dbytes(count) and ceil(count / 32) bytes.  Empty tensors may
+    be None."""
+    if len(src) != len(dst8) or len(src) != len(scl8):
+        raise ValueError("mx_quant_segments: src, dst8 and scl8 differ in length")
+    c = _norm_counts("mx_quant_segments", src, counts)
+    check(lib().bine_mx_quant_segments(len(src), _ptrs(src), _ptrs(dst8), _ptrs(scl8), c, _adamw_dtype(sdtype, src),
+                                       _mx(fmt), _stream(stream, None)), "bine_mx_quant_segments")
+
+
+def mx_dequant_segments(src8, scl8, dst, fmt, ddtype=None, counts=None, stream=None) -> None:
+    """dst[k] = the MX data src8[k] decoded exactly, times 2^(S - 127) of its
+    block's scale byte in float32, rounded once into dst's type
+    (bine_mx_dequant_segments); S = 0xFF gives quiet NaNs."""
+    if len(src8) != len(dst) or len(scl8) != len(dst):
+        raise ValueError("mx_dequant_segments: src8, scl8 and dst differ in length")
+    c = _norm_counts("mx_dequant_segments", dst, counts)
+    check(lib().bine_mx_dequant_segments(len(dst), _ptrs(src8), _ptrs(scl8), _ptrs(dst), c, _adamw_dtype(ddtype, dst),
+                                         _mx(fmt), _stream(stream, None)), "bine_mx_dequant_segments")
+
+
+def mx_quant_multi(ag_algo, params8, scales8, src, fmt, comm: Comm, sdtype=None, shard_counts=None, stream=None):
+    """bine_mx_quant_multi: this rank's shards src[k] quantized into its slots
+    of params8[k] (comm.size * mx_dbytes(shard_counts[k]) uint8) and scales8[k]
+    (comm.size * shard_counts[k] / 32 uint8), then ONE in-place allgather_multi
+    over the 2n buffers as uint8.  Every shard count a multiple of 32."""
+    if len(params8) != len(src) or len(scales8) != len(src):
+        raise ValueError("mx_quant_multi: params8, scales8 and src differ in length")
+    c = _norm_counts("mx_quant_multi", src, shard_counts)
+    check(lib().bine_mx_quant_multi(comm.handle, _algo("allgather", ag_algo), len(src), _ptrs(params8),
+                                    _ptrs(scales8), _ptrs(src), c, _adamw_dtype(sdtype, src), _mx(fmt),
+                                    _stream(stream, comm)), f"mx_quant_multi ({ag_algo})")
+
+
+def loopback_mx_quant_multi(comms, ag_algo, params8, scales8, src, fmt, sdtype=None, shard_counts=None):
+    """mx_quant_multi on every virtual rank: params8, scales8 and src one list
+    of tensors per rank, shard_counts one list for all ranks (None: rank 0's
+    numel()).  Returns (status, per-rank statuses)."""
+    P = len(comms)
+    n = len(src[0])
+    if any(len(x) != P for x in (params8, scales8, src)) or \
+            any(len(r) != n for x in (params8, scales8, src) for r in x):
+        raise ValueError("loopback_mx_quant_multi: the ranks' lists differ in length")
+    if shard_counts is None:
+        shard_counts = [t.numel() for t in src[0]]
+    flat = lambda x: [t for r in x for t in r]  # noqa: E731
+    st = (ctypes.c_int * P)()
+    hs = (ctypes.c_void_p * P)(*[c.handle.value for c in comms])
+    rc = lib().bine_loopback_run_mx_quant_multi(
+        hs, P, _algo("allgather", ag_algo), n, _ptrs(flat(params8)), _ptrs(flat(scales8)), _ptrs(flat(src)),
+        (ctypes.c_size_t * max(n, 1))(*shard_counts), _adamw_dtype(sdtype, flat(src)), _mx(fmt), st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -1586,6 +1688,8 @@ __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fus
            "adamw_multi_dyn", "loopback_adamw_multi_dyn",
            "amax_segments", "fp8_scales", "fp8_scale_host", "quant_segments", "dequant_segments", "plan_quant",
            "quant_multi", "loopback_quant_multi",
+           "mx_dbytes", "mx_scale_host", "plan_mx", "mx_quant_segments", "mx_dequant_segments", "mx_quant_multi",
+           "loopback_mx_quant_multi",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

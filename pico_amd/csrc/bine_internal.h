@@ -498,6 +498,59 @@ int launch_quant_segments_h16(const std::vector<QuantLaunch> &ls, const void *co
                               const size_t *counts, int sdtype, int fmt, const float *scales, void *stream);
 int launch_dequant_segments_h16(const std::vector<QuantLaunch> &ls, const void *const *src8, void *const *dst,
                                 const size_t *counts, int ddtype, int fmt, const float *inv_scales, void *stream);
+
+// MX block-scaled quantization of a list of tensors (bine_mx_quant_segments,
+// bine_mx_dequant_segments; kernels_h16.o): 32 elements share one E8M0 byte.
+// The scale rule of bine_amd.h -- ONE statement for the host twin
+// (bine_mx_scale_host, segments.cpp) and for k_mx_segs (kernels.hip), in
+// integer arithmetic on the pattern; tests/mx_sim.py restates it with frexp.
+constexpr int kMxBlock = 32;
+BINE_HOST_DEVICE constexpr int mx_emax(int fmt) { return fmt == BINE_MX_E4M3 ? 8 : fmt == BINE_MX_E5M2 ? 15 : 2; }
+inline bool mx_fmt_ok(int fmt) { return fmt == BINE_MX_E4M3 || fmt == BINE_MX_E5M2 || fmt == BINE_MX_E2M1; }
+// the data bytes of `count` elements: one each, or two per byte for E2M1
+BINE_HOST_DEVICE inline uint64_t mx_dbytes(uint64_t count, int fmt) {
+  return fmt == BINE_MX_E2M1 ? (count + 1) / 2 : count;
+}
+// A: the block's largest bits(widen(x)) & 0x7fffffff
+BINE_HOST_DEVICE inline uint8_t mx_scale_rule(uint32_t A, int fmt) {
+  if (A >= 0x7f800000u) return 0xff;  // an inf or a NaN in the block
+  if (A == 0) return 0;
+  // E = floor(log2 |max|); a subnormal is man * 2^-149 with its leading one at bit p
+  const int E = (A >> 23) ? (int)(A >> 23) - 127 : (31 - __builtin_clz(A)) - 149;
+  const int S = E - mx_emax(fmt) + 127;
+  return (uint8_t)(S < 0 ? 0 : S);
+}
+// k_mx_segs, both directions: tiles of kCopyTileVecs * 16 bytes of the WIDE
+// side counted from the segment's FIRST ELEMENT (blocks are, so a tile is whole
+// blocks), at least one per non-empty segment, with one body flag per slot.
+constexpr int kMxSegsPerLaunch = BINE_MX_SEGS_PER_LAUNCH;
+struct MxLaunch : LaunchTable<kMxSegsPerLaunch> {
+  uint64_t elem[(kMxSegsPerLaunch + 63) / 64] = {};  // bit s: slot s takes the element body
+};
+// the body of one segment: 0 vector -- wide on a 16-B boundary and data8 on a
+// boundary of the bytes one wide vector yields -- or 1 element
+inline int mx_body(uint64_t wide, uint64_t data8, size_t esz, int fmt) {
+  return wide % 16 || data8 % mx_dbytes(16 / esz, fmt) ? 1 : 0;
+}
+// the body flags of `ls` for other addresses of the same counts
+void mx_set_bodies(std::vector<MxLaunch> &ls, const void *const *wide, const void *const *data8, int dtype, int fmt);
+// The checks of the three lists that need no device, in the header's order
+// (dtype and fmt through the wide side's alignment), then the launches.
+int plan_mx_launches(int n, const uint64_t *wide, const uint64_t *data8, const uint64_t *scl8, const size_t *counts,
+                     int dtype, int fmt, std::vector<MxLaunch> &out);
+// Every check of the two entry points, nothing launched; BINE_SUCCESS or
+// BINE_ERR_ARG with *why = what was refused.  wide / data8: src / dst8 of
+// bine_mx_quant_segments, dst / src8 of bine_mx_dequant_segments.
+int mx_args(int n, const void *const *wide, const void *const *data8, const void *const *scl8, const size_t *counts,
+            int dtype, int fmt, const char **why, std::vector<MxLaunch> *ls);
+// bine_mx_quant_multi's checks that need no communicator and no algorithm id:
+// mx_args with params8 / scales8 standing for the slots, then the shard counts
+int mx_multi_args(int n, void *const *params8, void *const *scales8, const void *const *src,
+                  const size_t *shard_counts, int sdtype, int fmt, const char **why, std::vector<MxLaunch> *ls);
+int launch_mx_quant_segments_h16(const std::vector<MxLaunch> &ls, const void *const *src, void *const *dst8,
+                                 void *const *scl8, const size_t *counts, int sdtype, int fmt, void *stream);
+int launch_mx_dequant_segments_h16(const std::vector<MxLaunch> &ls, const void *const *src8, const void *const *scl8,
+                                   void *const *dst, const size_t *counts, int ddtype, int fmt, void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -2114,6 +2114,22 @@ int bine_dequant_segments(int n, const void *const *src8, void *const *dst, cons
   return launch_dequant_segments_h16(ls, src8, dst, counts, ddtype, fmt, inv_scales, stream);
 }
 
+int bine_mx_quant_segments(int n, const void *const *src, void *const *dst8, void *const *scl8,
+                           const size_t *counts, int sdtype, int fmt, void *stream) {
+  const char *why = nullptr;
+  std::vector<MxLaunch> ls;
+  if (const int rc = mx_args(n, src, dst8, scl8, counts, sdtype, fmt, &why, &ls)) return fp8_refused(__func__, rc, why);
+  return launch_mx_quant_segments_h16(ls, src, dst8, scl8, counts, sdtype, fmt, stream);
+}
+
+int bine_mx_dequant_segments(int n, const void *const *src8, const void *const *scl8, void *const *dst,
+                             const size_t *counts, int ddtype, int fmt, void *stream) {
+  const char *why = nullptr;
+  std::vector<MxLaunch> ls;
+  if (const int rc = mx_args(n, dst, src8, scl8, counts, ddtype, fmt, &why, &ls)) return fp8_refused(__func__, rc, why);
+  return launch_mx_dequant_segments_h16(ls, src8, scl8, dst, counts, ddtype, fmt, stream);
+}
+
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream) {
   return launch_fill_pico(buf, count, dtype, seed, stream);
 }
@@ -2864,6 +2880,47 @@ int bine_quant_multi(bine_comm_t c, int amax_algo, int ag_algo, int n, void *con
   return bine_allgather_multi(c, ag_algo, n, nullptr, params8, shard_counts, BINE_UINT8, K);
 }
 
+// ---- MX block-scaled parameter allgather of a bucket (bine_amd.h) ---------------------------
+
+// the checks that need no communicator, in the header's order.  ls: the launches
+// over src (the body flags are params8's: the caller sets its slots', mx_set_bodies)
+static int mx_quant_multi_args(int ag_algo, int n, void *const *params8, void *const *scales8,
+                               const void *const *src, const size_t *shard_counts, int sdtype, int fmt,
+                               const char **why, std::vector<MxLaunch> *ls = nullptr) {
+  if (const int rc = mx_multi_args(n, params8, scales8, src, shard_counts, sdtype, fmt, why, ls)) return rc;
+  if (ag_algo < BINE_AG_RECURSIVEDOUBLING || ag_algo > BINE_AG_BINE_2_BLOCKS_DTYPE) {
+    *why = "ag_algo outside the allgather range";
+    return BINE_ERR_UNSUPPORTED;
+  }
+  return BINE_SUCCESS;
+}
+
+int bine_mx_quant_multi(bine_comm_t c, int ag_algo, int n, void *const *params8, void *const *scales8,
+                        const void *const *src, const size_t *shard_counts, int sdtype, int fmt, void *stream) {
+  const char *why = nullptr;
+  std::vector<MxLaunch> ls;
+  if (const int rc = mx_quant_multi_args(ag_algo, n, params8, scales8, src, shard_counts, sdtype, fmt, &why, &ls))
+    return fp8_refused(__func__, rc, why);
+  if (!c) return fp8_refused(__func__, BINE_ERR_ARG, "comm NULL");
+  size_t total = 0;
+  for (int k = 0; k < n; k++) total += shard_counts[k];
+  if (total == 0) return BINE_SUCCESS;
+  // this rank's slots of both lists, then the 2n buffers of the one allgather
+  std::vector<void *> dst8((size_t)n), scl8((size_t)n), bufs(2 * (size_t)n);
+  std::vector<size_t> bytes(2 * (size_t)n);
+  for (int k = 0; k < n; k++) {
+    const size_t db = (size_t)mx_dbytes(shard_counts[k], fmt), sb = shard_counts[k] / kMxBlock;
+    dst8[k] = shard_counts[k] ? (char *)params8[k] + (size_t)c->rank * db : nullptr;
+    scl8[k] = shard_counts[k] ? (char *)scales8[k] + (size_t)c->rank * sb : nullptr;
+    bufs[k] = params8[k], bufs[(size_t)n + k] = scales8[k];
+    bytes[k] = db, bytes[(size_t)n + k] = sb;
+  }
+  mx_set_bodies(ls, src, dst8.data(), sdtype, fmt);
+  if (const int rc = launch_mx_quant_segments_h16(ls, src, dst8.data(), scl8.data(), shard_counts, sdtype, fmt, stream))
+    return rc;
+  return bine_allgather_multi(c, ag_algo, 2 * n, nullptr, bufs.data(), bytes.data(), BINE_UINT8, stream);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -3235,6 +3292,26 @@ int bine_loopback_run_quant_multi(bine_comm_t *comms, int nranks, int amax_algo,
     (void)hipSetDevice(comms[r]->device);
     return bine_quant_multi(comms[r], amax_algo, ag_algo, n, at(params8, r), at(src, r), shard_counts, sdtype, fmt,
                             scales[r], comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_mx_quant_multi(bine_comm_t *comms, int nranks, int ag_algo, int n, void *const *params8,
+                                     void *const *scales8, const void *const *src, const size_t *shard_counts,
+                                     int sdtype, int fmt, int *statuses) {
+  auto at = [&](auto *list, int r) { return list && n > 0 ? list + (size_t)r * n : list; };
+  // before any thread, stream or HIP call: what a rank would refuse without a communicator
+  const char *why = nullptr;
+  int bad = BINE_SUCCESS;
+  for (int r = 0; !bad && r < nranks; r++)
+    bad = mx_quant_multi_args(ag_algo, n, at(params8, r), at(scales8, r), at(src, r), shard_counts, sdtype, fmt, &why);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return fp8_refused(__func__, bad, why);
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_mx_quant_multi(comms[r], ag_algo, n, at(params8, r), at(scales8, r), at(src, r), shard_counts, sdtype,
+                               fmt, comms[r]->stream);
   });
 }
 

@@ -45,9 +45,9 @@
 // instantiations for the 16-bit floating types (launch_*_h16, reached the
 // same way) and, for those types alone, the wide kernels k_widen / k_narrow /
 // k_reduce_tree_wide (launch_*_h16, called directly: no other compilation
-// holds a wide kernel), k_adamw_segs and the FP8 kernels k_amax_segs /
-// k_fp8_scales / k_quant_segs, which need the same widen1 / narrow1.  Three
-// translation units compile in parallel.
+// holds a wide kernel), k_adamw_segs, the FP8 kernels k_amax_segs /
+// k_fp8_scales / k_quant_segs and the MX kernel k_mx_segs, which need the same
+// widen1 / narrow1.  Three translation units compile in parallel.
 //
 // Adding an element type: (1) a case in with_dtype, under the BINE_OPSET of
 // the compilation that is to hold it -- every reduce-family entry point, the
@@ -2693,6 +2693,289 @@ int launch_quant_segments_h16(const std::vector<QuantLaunch> &ls, const void *co
 int launch_dequant_segments_h16(const std::vector<QuantLaunch> &ls, const void *const *src8, void *const *dst,
                                 const size_t *counts, int ddtype, int fmt, const float *inv_scales, void *stream) {
   return quant_issue<true>(ls, dst, src8, counts, ddtype, fmt, inv_scales, stream);
+}
+
+// ----------------------------------------------------------------------------
+// MX block-scaled quantization of a list of tensors (bine_amd.h): k_mx_segs,
+// which also dequantizes.  TileTable's dispatch over plan_mx_launches' table of
+// the WIDE side; here a tile is kBlock * kScaleU 16-B vectors counted from the
+// segment's FIRST ELEMENT, as the 32-element blocks are, so a tile is whole
+// blocks and a workgroup owns its tile's blocks, data bytes and scale bytes.
+// No LDS, no atomics: a block lives in 8 (float) or 4 (16-bit) adjacent lanes
+// of the vector body, in 32 adjacent lanes of the element body.
+
+// the maximum of v over the 2^LOG adjacent lanes that hold one block, valid in
+// each of them (LOG <= 5).  DPP within a row of 16: two quad permutations leave
+// a quad agreeing, the half-row mirror then brings the other quad's value, the
+// row mirror the other half's; the 32-lane step crosses rows by a shuffle.
+template <int LOG>
+__device__ __forceinline__ uint32_t mx_group_max(uint32_t v) {
+  auto step = [&](int o) { v = (uint32_t)o > v ? (uint32_t)o : v; };
+  if constexpr (LOG >= 1) step(__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
+  if constexpr (LOG >= 2) step(__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
+  if constexpr (LOG >= 3) step(__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false));  // row_half_mirror
+  if constexpr (LOG >= 4) step(__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false));  // row_mirror
+  if constexpr (LOG >= 5) step(__shfl_xor((int)v, 16, 64));
+  return v;
+}
+
+// 2^(127 - S), the quantizer's factor (S <= 252: a normal number), and 2^(S -
+// 127), the dequantizer's (S <= 254; at S = 0 the subnormal 2^-127)
+__device__ __forceinline__ float mx_qfactor(uint32_t S) {
+  const uint32_t b = (254u - S) << 23;
+  float f;
+  __builtin_memcpy(&f, &b, 4);
+  return f;
+}
+__device__ __forceinline__ float mx_dfactor(uint32_t S) {
+  const uint32_t b = S ? S << 23 : 0x00400000u;
+  float f;
+  __builtin_memcpy(&f, &b, 4);
+  return f;
+}
+
+// y (never NaN here) as an E2M1 nibble: nearest with ties to the even code by
+// counting the thresholds passed -- the midpoints of 0, 0.5, 1, 1.5, 2, 3, 4,
+// 6, each closed on the side of its even neighbour; everything above 5 is 6,
+// which is the clamp.  Plain comparisons, so the contract's bits by
+// construction (DESIGN.md 6.10 has what v_cvt_scalef32_pk_fp4_f32 was found
+// to do on the same inputs, tools/mx_variants.hip).
+__device__ __forceinline__ uint32_t fp4_enc1(float y) {
+  uint32_t b;
+  __builtin_memcpy(&b, &y, 4);
+  const float a = __builtin_fabsf(y);
+  const uint32_t c = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
+                     (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+  return c | ((b >> 28) & 8u);
+}
+// the nibble as the binary32 pattern of its value, exactly
+__device__ __forceinline__ uint32_t fp4_decode_bits(uint32_t nib) {
+  const uint32_t m = nib & 7u, sgn = (nib & 8u) << 28;
+  if (m < 2) return sgn | (m ? 0x3f000000u : 0u);                // 0, 0.5 (the subnormal)
+  return sgn | (((m >> 1) + 126u) << 23) | ((m & 1u) << 22);  // 1.f * 2^(e - 1)
+}
+
+// the data bytes of one 16-B wide vector: FP8 one word for float and two for
+// the 16-bit types; E2M1 half of that
+template <typename T, int FMT>
+using mxw_of = std::conditional_t<FMT != BINE_MX_E2M1, q8_of<T>,
+                                  std::conditional_t<sizeof(T) == 4, uint16_t, uint32_t>>;
+
+// one element: the byte (FP8) or the nibble (E2M1) of widen(x) * 2^(127 - S); S != 0xFF
+template <typename T, int FMT>
+__device__ __forceinline__ uint32_t mx_quant1(T x, uint32_t S) {
+  const float y = adamw_widen<T>(x) * mx_qfactor(S);
+  if constexpr (FMT == BINE_MX_E2M1) return fp4_enc1(y);
+  else return quant4<FMT>(y, 0.0f, 0.0f, 0.0f) & 0xffu;
+}
+template <typename T, int FMT>
+__device__ __forceinline__ mxw_of<T, FMT> mx_quant16(u32x4 v, uint32_t S) {
+  constexpr int V = 16 / (int)sizeof(T);
+  float y[V];
+  const float f = mx_qfactor(S);
+  if constexpr (sizeof(T) == 4) {
+    __builtin_memcpy(y, &v, 16);
+  } else {
+    const W8 w = widen16<T>(v);
+    __builtin_memcpy(y, &w.a, 16);
+    __builtin_memcpy(y + 4, &w.b, 16);
+  }
+#pragma unroll
+  for (int j = 0; j < V; j++) y[j] *= f;
+  uint32_t w[V / 4] = {};
+  if constexpr (FMT == BINE_MX_E2M1) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int j = 0; j < V; j++) r |= fp4_enc1(y[j]) << (4 * j);
+    return S == 0xffu ? (mxw_of<T, FMT>)0 : (mxw_of<T, FMT>)r;
+  } else {
+#pragma unroll
+    for (int j = 0; j < V / 4; j++)
+      w[j] = S == 0xffu ? 0u : quant4<FMT>(y[4 * j], y[4 * j + 1], y[4 * j + 2], y[4 * j + 3]);
+    mxw_of<T, FMT> r;
+    __builtin_memcpy(&r, w, sizeof r);
+    return r;
+  }
+}
+
+// data byte (nibble) b of a block with scale byte S as an element of T (its pattern)
+template <typename T, int FMT>
+__device__ __forceinline__ uint_of<T> mx_dequant1(uint32_t b, uint32_t S) {
+  if (S == 0xffu) {
+    if constexpr (std::is_same_v<T, float>) return 0x7fc00000u;
+    else if constexpr (std::is_same_v<T, BF16>) return (uint16_t)0x7fc0u;
+    else return (uint16_t)0x7e00u;
+  }
+  if constexpr (FMT == BINE_MX_E2M1) {
+    const uint32_t d = fp4_decode_bits(b);
+    float f;
+    __builtin_memcpy(&f, &d, 4);
+    const T t = adamw_narrow<T>(f * mx_dfactor(S));
+    uint_of<T> r;
+    __builtin_memcpy(&r, &t, sizeof r);
+    return r;
+  } else {
+    return dequant1<T, FMT>(b, mx_dfactor(S));
+  }
+}
+template <typename T, int FMT>
+__device__ __forceinline__ u32x4 mx_dequant16(mxw_of<T, FMT> b, uint32_t S) {
+  constexpr int V = 16 / (int)sizeof(T), BITS = FMT == BINE_MX_E2M1 ? 4 : 8;
+  uint32_t w[2] = {};
+  __builtin_memcpy(w, &b, sizeof b);
+  uint_of<T> e[V];
+#pragma unroll
+  for (int j = 0; j < V; j++)
+    e[j] = mx_dequant1<T, FMT>((w[j * BITS / 32] >> (j * BITS % 32)) & ((1u << BITS) - 1), S);
+  u32x4 r;
+  __builtin_memcpy(&r, e, 16);
+  return r;
+}
+
+// One descriptor per slot: the wide buffer, the data bytes, the scale bytes,
+// the element count.
+struct MxSeg {
+  uint8_t *wide, *d8, *sc;
+  uint64_t n;  // elements
+};
+struct MxSegs {
+  TileTable<kMxSegsPerLaunch> tab;
+  uint64_t elem[(kMxSegsPerLaunch + 63) / 64];  // bit s: slot s takes the element body
+  MxSeg s[kMxSegsPerLaunch];
+};
+static_assert(sizeof(MxSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+static_assert(kCopyTileVecs == (uint64_t)kBlock * kScaleU, "plan_mx_launches' tile is this kernel's");
+
+// DEQ false: (d8, sc) = quantize(wide); true: wide = dequantize(d8, sc)
+template <typename T, int FMT, bool DEQ>
+__global__ __launch_bounds__(kBlock) void k_mx_segs(MxSegs a) {
+  constexpr size_t V = 16 / sizeof(T);        // elements of one vector
+  constexpr int LOG = sizeof(T) == 4 ? 3 : 2;  // log2 of the lanes that hold one block (32 / V)
+  constexpr size_t TV = (size_t)kBlock * kScaleU;
+  using DW = mxw_of<T, FMT>;
+  const auto [k, wt] = a.tab.find(blockIdx.x);
+  T *wide = reinterpret_cast<T *>(a.s[k].wide);
+  uint8_t *d8 = a.s[k].d8, *sc = a.s[k].sc;
+  const size_t n = a.s[k].n;
+  const bool elem = (a.elem[k >> 6] >> (k & 63)) & 1;
+  // the tile's elements [lo, hi); the vector body takes its whole blocks [lo, vend)
+  const size_t lo = (size_t)wt * TV * V;
+  const size_t hi = lo + TV * V < n ? lo + TV * V : n;
+  const size_t vend = elem ? lo : hi & ~(size_t)(kMxBlock - 1);
+  if (vend > lo) {
+    const size_t nv = (vend - lo) / V;  // a multiple of the lanes of a block
+    u32x4 *vw = reinterpret_cast<u32x4 *>(wide) + lo / V;
+    DW *vd = reinterpret_cast<DW *>(d8) + lo / V;
+    uint8_t *vs = sc + lo / kMxBlock;
+    const size_t t = threadIdx.x;
+    if (nv == TV) {  // a full tile: every load issued before the first use
+      if constexpr (DEQ) {
+        DW xb[kScaleU];
+        uint32_t S[kScaleU];
+#pragma unroll
+        for (int u = 0; u < kScaleU; u++) {
+          xb[u] = __builtin_nontemporal_load(vd + t + (size_t)u * kBlock);
+          S[u] = __builtin_nontemporal_load(vs + ((t + (size_t)u * kBlock) >> LOG));
+        }
+#pragma unroll
+        for (int u = 0; u < kScaleU; u++)
+          __builtin_nontemporal_store(mx_dequant16<T, FMT>(xb[u], S[u]), vw + t + (size_t)u * kBlock);
+      } else {
+        u32x4 xw[kScaleU];
+#pragma unroll
+        for (int u = 0; u < kScaleU; u++) xw[u] = __builtin_nontemporal_load(vw + t + (size_t)u * kBlock);
+#pragma unroll
+        for (int u = 0; u < kScaleU; u++) {
+          const size_t i = t + (size_t)u * kBlock;
+          const uint32_t S = mx_scale_rule(widen_bits<T>(mx_group_max<LOG>(mag16<T>(xw[u]))), FMT);
+          __builtin_nontemporal_store(mx_quant16<T, FMT>(xw[u], S), vd + i);
+          if ((t & ((1u << LOG) - 1)) == 0) __builtin_nontemporal_store((uint8_t)S, vs + (i >> LOG));
+        }
+      }
+    } else {
+#pragma unroll 1
+      for (int u = 0; u < kScaleU; u++) {
+        const size_t i = t + (size_t)u * kBlock;
+        const bool in = i < nv;  // the same in all lanes of a block
+        if constexpr (DEQ) {
+          if (in) __builtin_nontemporal_store(mx_dequant16<T, FMT>(vd[i], vs[i >> LOG]), vw + i);
+        } else {
+          // every lane takes part in the cross-lane maximum: the loads and the stores are guarded, not it
+          u32x4 x = {0, 0, 0, 0};
+          if (in) x = vw[i];
+          const uint32_t S = mx_scale_rule(widen_bits<T>(mx_group_max<LOG>(mag16<T>(x))), FMT);
+          if (in) {
+            __builtin_nontemporal_store(mx_quant16<T, FMT>(x, S), vd + i);
+            if ((t & ((1u << LOG) - 1)) == 0) __builtin_nontemporal_store((uint8_t)S, vs + (i >> LOG));
+          }
+        }
+      }
+    }
+  }
+  // the element body: [vend, hi), one element per lane, 32 adjacent lanes a
+  // block (vend is a block's first element and kBlock a multiple of 32); the
+  // lanes of a block leave the loop together
+  const uint_of<T> *wb = reinterpret_cast<const uint_of<T> *>(wide);
+#pragma unroll 1
+  for (size_t i = vend + threadIdx.x; (i & ~(size_t)(kMxBlock - 1)) < hi; i += kBlock) {
+    const bool in = i < hi;
+    if constexpr (DEQ) {
+      if (in) {
+        const uint32_t S = sc[i / kMxBlock];
+        const uint32_t b = FMT == BINE_MX_E2M1 ? (d8[i >> 1] >> (4 * (i & 1))) & 15u : d8[i];
+        __builtin_nontemporal_store(mx_dequant1<T, FMT>(b, S), reinterpret_cast<uint_of<T> *>(wide) + i);
+      }
+    } else {
+      uint_of<T> xb = 0;
+      if (in) xb = wb[i];
+      const uint32_t m = (uint32_t)xb & (sizeof(T) == 4 ? 0x7fffffffu : 0x7fffu);
+      const uint32_t S = mx_scale_rule(widen_bits<T>(mx_group_max<5>(m)), FMT);
+      T x;
+      __builtin_memcpy(&x, &xb, sizeof x);
+      const uint32_t q = S == 0xffu ? 0u : mx_quant1<T, FMT>(x, S);  // a lane past the end: +0, code 0
+      if constexpr (FMT == BINE_MX_E2M1) {
+        const uint32_t other = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q, 0xB1, 0xf, 0xf, false);  // lane ^ 1
+        if (in && !(i & 1)) __builtin_nontemporal_store((uint8_t)(q | (other << 4)), d8 + (i >> 1));
+      } else {
+        if (in) __builtin_nontemporal_store((uint8_t)q, d8 + i);
+      }
+      if ((i & (kMxBlock - 1)) == 0) __builtin_nontemporal_store((uint8_t)S, sc + i / kMxBlock);
+    }
+  }
+}
+
+template <bool DEQ>
+static int mx_issue(const std::vector<MxLaunch> &ls, const void *const *wide, const void *const *d8,
+                    const void *const *sc, const size_t *counts, int dtype, int fmt, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  return with_adamw_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    for (const MxLaunch &L : ls) {
+      MxSegs a;
+      for (size_t w = 0; w < sizeof a.elem / sizeof a.elem[0]; w++) a.elem[w] = L.elem[w];
+      fill_segs(a, L, [&](int s) {
+        const int k = L.seg[s];
+        return MxSeg{(uint8_t *)const_cast<void *>(wide[k]), (uint8_t *)const_cast<void *>(d8[k]),
+                     (uint8_t *)const_cast<void *>(sc[k]), (uint64_t)counts[k]};
+      });
+      const dim3 grid(L.tile0[L.nseg]), blk(kBlock);
+      if (fmt == BINE_MX_E4M3) hipLaunchKernelGGL((k_mx_segs<T, BINE_MX_E4M3, DEQ>), grid, blk, 0, st, a);
+      else if (fmt == BINE_MX_E5M2) hipLaunchKernelGGL((k_mx_segs<T, BINE_MX_E5M2, DEQ>), grid, blk, 0, st, a);
+      else hipLaunchKernelGGL((k_mx_segs<T, BINE_MX_E2M1, DEQ>), grid, blk, 0, st, a);
+      if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+    }
+    return BINE_SUCCESS;
+  });
+}
+
+int launch_mx_quant_segments_h16(const std::vector<MxLaunch> &ls, const void *const *src, void *const *dst8,
+                                 void *const *scl8, const size_t *counts, int sdtype, int fmt, void *stream) {
+  return mx_issue<false>(ls, src, dst8, scl8, counts, sdtype, fmt, stream);
+}
+
+int launch_mx_dequant_segments_h16(const std::vector<MxLaunch> &ls, const void *const *src8, const void *const *scl8,
+                                   void *const *dst, const size_t *counts, int ddtype, int fmt, void *stream) {
+  return mx_issue<true>(ls, dst, src8, scl8, counts, ddtype, fmt, stream);
 }
 #endif  // BINE_OPSET == 2
 

@@ -18,11 +18,18 @@
 //                                            refusals (amax_args, fp8_scales_args, quant_args) and
 //                                            bine_fp8_scale_host, the host compilation of fp8_scale_rule
 //                                            (tools/quant_check.cpp)
+//   plan_mx_launches / bine_plan_mx          k_mx_segs (both directions): a table of its own over the wide
+//                                            side, tiles counted from the segment's first element as MX
+//                                            blocks are, kMxSegsPerLaunch descriptors per launch, one body
+//                                            flag per slot; the MX calls' refusals (mx_args, mx_multi_args)
+//                                            and bine_mx_scale_host, the host compilation of mx_scale_rule
+//                                            (tools/mx_check.cpp)
 // Dynamic loss scaling keeps its host half here too:
 // bine_step_state_init, the refusals (step_update_args, adamw_dyn_args) and
 // bine_step_update_host, the host compilation of the statement k_step_update
 // runs (step_update_rule, bine_internal.h; tools/step_check.cpp).
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
 #include "bine_internal.h"
@@ -314,6 +321,73 @@ int quant_args(int n, const void *const *wide, const void *const *bytes8, const 
   return BINE_SUCCESS;
 }
 
+
+int plan_mx_launches(int n, const uint64_t *wide, const uint64_t *data8, const uint64_t *scl8, const size_t *counts,
+                     int dtype, int fmt, std::vector<MxLaunch> &out) {
+  out.clear();
+  const size_t esz = adamw_esz(dtype);
+  if (!esz || !mx_fmt_ok(fmt)) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX) return BINE_ERR_ARG;
+  if (n > 0 && (!wide || !data8 || !scl8 || !counts)) return BINE_ERR_ARG;
+  for (int k = 0; k < n; k++)
+    if (counts[k] && (!wide[k] || !data8[k] || !scl8[k])) return BINE_ERR_ARG;
+  for (int k = 0; k < n; k++) {
+    if (counts[k] && wide[k] % esz) return BINE_ERR_ARG;
+    if (counts[k] > ((size_t)1 << 56)) return BINE_ERR_ARG;  // keeps the byte count and every sum below 2^64
+  }
+  const uint64_t tile_elems = kCopyTileVecs * 16 / esz;  // whole blocks: a multiple of kMxBlock
+  for (int k = 0; k < n; k++) {
+    if (counts[k] == 0) continue;
+    const uint64_t tiles = (counts[k] + tile_elems - 1) / tile_elems;
+    if (tiles > kSegMaxWgs) return BINE_ERR_ARG;
+    if (out.empty() || out.back().nseg == kMxSegsPerLaunch || out.back().tile0[out.back().nseg] + tiles > kSegMaxWgs)
+      out.emplace_back();
+    MxLaunch &L = out.back();
+    const int s = L.nseg++;
+    L.seg[s] = k;
+    L.tile0[s + 1] = (uint32_t)(L.tile0[s] + tiles);
+    if (mx_body(wide[k], data8[k], esz, fmt)) L.elem[s >> 6] |= (uint64_t)1 << (s & 63);
+  }
+  return BINE_SUCCESS;
+}
+
+void mx_set_bodies(std::vector<MxLaunch> &ls, const void *const *wide, const void *const *data8, int dtype, int fmt) {
+  const size_t esz = adamw_esz(dtype);
+  for (MxLaunch &L : ls) {
+    for (uint64_t &w : L.elem) w = 0;
+    for (int s = 0; s < L.nseg; s++) {
+      const int k = L.seg[s];
+      if (mx_body((uint64_t)(uintptr_t)wide[k], (uint64_t)(uintptr_t)data8[k], esz, fmt))
+        L.elem[s >> 6] |= (uint64_t)1 << (s & 63);
+    }
+  }
+}
+
+int mx_args(int n, const void *const *wide, const void *const *data8, const void *const *scl8, const size_t *counts,
+            int dtype, int fmt, const char **why, std::vector<MxLaunch> *ls) {
+  if (!adamw_esz(dtype)) return refuse(why, "dtype: float, float16 or bfloat16");
+  if (!mx_fmt_ok(fmt)) return refuse(why, "fmt: BINE_MX_E4M3, BINE_MX_E5M2 or BINE_MX_E2M1");
+  std::vector<uint64_t> a;  // wide, data8, scl8
+  if (seg_list_addrs(n, counts, {wide, data8, scl8}, a))
+    return refuse(why, "n outside [0, BINE_MULTI_MAX], or a NULL array");
+  std::vector<MxLaunch> local;
+  if (plan_mx_launches(n, a.data(), a.data() + n, a.data() + 2 * (size_t)n, counts, dtype, fmt, ls ? *ls : local))
+    return refuse(why, "a NULL buffer with a non-zero count, or a wide buffer not aligned to its element");
+  return BINE_SUCCESS;
+}
+
+int mx_multi_args(int n, void *const *params8, void *const *scales8, const void *const *src,
+                  const size_t *shard_counts, int sdtype, int fmt, const char **why, std::vector<MxLaunch> *ls) {
+  if (!adamw_esz(sdtype)) return refuse(why, "sdtype: float, float16 or bfloat16");
+  if (!mx_fmt_ok(fmt)) return refuse(why, "fmt: BINE_MX_E4M3, BINE_MX_E5M2 or BINE_MX_E2M1");
+  if (n < 0 || n > BINE_MULTI_MAX / 2) return refuse(why, "n outside [0, BINE_MULTI_MAX / 2]");
+  if (const int rc = mx_args(n, src, params8, scales8, shard_counts, sdtype, fmt, why, ls)) return rc;
+  for (int k = 0; k < n; k++)
+    if (shard_counts[k] % kMxBlock || shard_counts[k] > (size_t)INT_MAX)
+      return refuse(why, "a shard count not a multiple of 32, or above INT_MAX");
+  return BINE_SUCCESS;
+}
+
 }  // namespace bine
 
 extern "C" int bine_fp8_scale_host(uint32_t amax_bits, int fmt, float *scale, float *inv) {
@@ -335,6 +409,30 @@ extern "C" int64_t bine_plan_quant(int n, const uint64_t *wide, const uint64_t *
         uint64_t *e = out + 5 * nt;
         e[0] = l, e[1] = (uint64_t)Q.seg[s], e[2] = Q.tile0[s], e[3] = Q.tile0[s + 1] - Q.tile0[s];
         e[4] = (Q.elem[s >> 6] >> (s & 63)) & 1;
+      }
+  }
+  return nt;
+}
+
+extern "C" int bine_mx_scale_host(uint32_t amax_bits, int fmt, uint8_t *s) {
+  if (!bine::mx_fmt_ok(fmt) || !s) return BINE_ERR_ARG;
+  *s = bine::mx_scale_rule(amax_bits, fmt);
+  return BINE_SUCCESS;
+}
+
+extern "C" int64_t bine_plan_mx(int n, const uint64_t *wide, const uint64_t *data8, const uint64_t *scl8,
+                                const size_t *counts, int dtype, int fmt, uint64_t *out, int64_t cap) {
+  std::vector<bine::MxLaunch> ls;
+  const int rc = bine::plan_mx_launches(n, wide, data8, scl8, counts, dtype, fmt, ls);
+  if (rc) return -(int64_t)rc;
+  int64_t nt = 0;
+  for (size_t l = 0; l < ls.size(); l++) {
+    const bine::MxLaunch &L = ls[l];
+    for (int s = 0; s < L.nseg; s++, nt++)
+      if (out && nt < cap) {
+        uint64_t *e = out + 5 * nt;
+        e[0] = l, e[1] = (uint64_t)L.seg[s], e[2] = L.tile0[s], e[3] = L.tile0[s + 1] - L.tile0[s];
+        e[4] = (L.elem[s >> 6] >> (s & 63)) & 1;
       }
   }
   return nt;

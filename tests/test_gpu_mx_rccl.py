@@ -1,0 +1,31 @@
+"""The MX block-scaled parameter allgather over the RCCL and direct transports in
+real processes, graph mode included (tools/mx_check.py)."""
+import os
+import sys
+
+import pytest
+
+import _sub
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# tools/quant_check.py's limit: the same forms, the same process start-up
+TIMEOUT = {2: 60}
+
+
+@pytest.mark.timeout(200)
+@pytest.mark.parametrize("P", [2])
+def test_mx_processes(P):
+    """P processes on the one GPU, the shards of six tensors each: mx_quant_multi
+    (float to e4m3 and bfloat16 to e2m1; ring) over RCCL P2P (literal and flat)
+    and over the direct transport, then twice in graph mode; every rank's
+    params8 and scales8 vs tests/mx_sim.py's two steps over all ranks' shards"""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    # 4 HW queues per rank, HIP's default: with fewer, graph mode keeps a call that
+    # makes RCCL calls eager and the tool's replay case would have nothing to replay
+    r = _sub.run_kw([sys.executable, "-u", os.path.join(ROOT, "tools", "mx_check.py"), str(P)], env=env,
+                    capture_output=True, text=True, timeout=TIMEOUT[P], ranks=P, queues=4)
+    lines = [x for x in r.stdout.splitlines() if "MISMATCH" in x or "RESULT" in x or " ok, " in x]
+    assert r.returncode == 0, "\n".join(lines[:40]) + "\n" + r.stderr[-2000:]
+    assert f"RESULT P={P}" in r.stdout
