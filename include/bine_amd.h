@@ -767,6 +767,67 @@ int bine_mx_dequant_segments(int n, const void *const *src8, const void *const *
                              const size_t *counts, int ddtype, int fmt, void *stream);
 int64_t bine_plan_mx(int n, const uint64_t *wide, const uint64_t *data8, const uint64_t *scl8, const size_t *counts,
                      int dtype, int fmt, uint64_t *out, int64_t cap);
+/* ---- MX wire blocks and their ordered binary32 sum -----------------------------------
+ * The receiving side of a quantized gradient exchange (bine_mx_reduce_scatter_multi,
+ * below with the collectives): P quantized contributions to one bucket of shards,
+ * decoded and summed into the shards.
+ *
+ * The wire layout of a bucket of n tensors with counts c_k (every c_k a multiple
+ * of 32, zero allowed) in format fmt: D = sum of dbytes(c_k), S = sum of c_k / 32,
+ * B = D + S rounded up to a multiple of 16.  One BLOCK of B bytes holds one
+ * contribution: tensor k's data bytes at the prefix sum of dbytes before k
+ * (always a multiple of 16), its scale bytes at D + the prefix sum of c_i / 32
+ * before k; the pad bytes behind D + S are never read as data.
+ * bine_mx_wire_bytes (host only): *data_bytes = D, *block_bytes = B.
+ * BINE_ERR_ARG: fmt; n < 0; data_bytes or block_bytes NULL; shard_counts NULL
+ * with n > 0; a count not a multiple of 32; a sum that overflows.
+ *
+ * bine_mx_sum_segments: `packed` holds nstreams (1 .. 16, no communicator is
+ * involved) blocks in that layout, stream j at packed + j * block_bytes.  For
+ * tensor k and element i, with b = i / 32:
+ *   d_j = decode(data_j[i]) * 2^(S_j[b] - 127)   one binary32 multiplication, exact
+ *         for all three formats under every scale byte the quantizer writes (S <=
+ *         246 / 239 / 252): the smallest product is 2^-143, above 2^-149,
+ *         subnormals kept, the largest FMAX * 2^(S - 127) < 2^128; a scale byte
+ *         placed by hand above that range can overflow to infinity, IEEE's
+ *   acc = d_0, then acc = acc + d_j for j = 1, 2, ... in that order, each step
+ *         one binary32 addition
+ *   dst[k][i] = narrow(acc * float32(scale))     one multiplication, one rounding
+ *         to nearest even into ddtype (float, float16 or bfloat16)
+ * Wherever d_j is exact, fma(decode, 2^(S - 127), acc) and multiply-then-add give
+ * the same bits; the kernel multiplies, then adds -- which is also what defines
+ * the hand-placed overflow case.  If any stream's scale byte
+ * of the block is 0xFF, all 32 outputs of the block are ddtype's positive quiet
+ * NaN (bine_mx_dequant_segments' patterns).  A NaN or infinity DATA byte placed
+ * by hand gives a NaN or an infinity by ordinary arithmetic; a NaN's payload
+ * and sign are not specified.  Arbitrary input bytes are legal.
+ * Mechanism: k_mx_sum_segs over bine_mx_dequant_segments' tile table of the
+ * DESTINATION (tiles of 32 KiB of dst counted from the segment's first element:
+ * whole blocks), BINE_MX_SEGS_PER_LAUNCH descriptors (a pointer, two offsets and
+ * a count) per launch by value.  A segment whose dst is 16-B aligned takes the
+ * vector body: a lane owns the run of elements whose data is one 16-B load per
+ * stream (16 of FP8, one whole block of E2M1), issues all nstreams data loads
+ * and scale-byte loads before the first use, all non-temporal, accumulates in
+ * registers and stores whole 16-B vectors.  Any other segment takes the
+ * element body: one element per lane, byte loads.  No LDS, no atomics, no
+ * barrier; the stream count is a run-time bound.  BINE_ERR_ARG, before any
+ * HIP call, in this order: ddtype or fmt; n < 0 or n > BINE_MULTI_MAX; dst or
+ * counts NULL with n > 0; a NULL buffer with a non-zero count; a destination not
+ * aligned to its element size; a count not a multiple of 32; nstreams outside
+ * [1, 16]; and, unless every count is 0: packed NULL or not 16-B aligned,
+ * block_bytes not a multiple of 16 or below bine_mx_wire_bytes' B.  With n = 0
+ * or every count 0 the call succeeds and writes nothing.  dst ranges must not
+ * overlap packed (not checked).
+ *
+ * bine_plan_mx_sum (host only): the launches bine_mx_sum_segments issues for
+ * these destinations, records as bine_plan_mx's (launch, segment, first
+ * workgroup, workgroups, body: 0 vector / 1 element). */
+#define BINE_MX_SUM_MAX_STREAMS 16
+int bine_mx_wire_bytes(int n, const size_t *shard_counts, int fmt, size_t *data_bytes, size_t *block_bytes);
+int bine_mx_sum_segments(int n, int nstreams, const void *packed, size_t block_bytes, void *const *dst,
+                         const size_t *counts, int ddtype, int fmt, double scale, void *stream);
+int64_t bine_plan_mx_sum(int n, const uint64_t *dst, const size_t *counts, int ddtype, int fmt, uint64_t *out,
+                         int64_t cap);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -1302,10 +1363,51 @@ int bine_quant_multi(bine_comm_t comm, int amax_algo, int ag_algo, int n, void *
  * to its element size; a shard count not a multiple of 32, or above INT_MAX
  * (all BINE_ERR_ARG); ag_algo outside the allgather range
  * (BINE_ERR_UNSUPPORTED); comm == NULL (BINE_ERR_ARG).  Step 2 returns whatever
- * the single call refuses.  Not provided: MX gradients in the reduce-scatter,
- * the store fused into k_adamw_segs. */
+ * the single call refuses.  Not provided: the store fused into k_adamw_segs. */
 int bine_mx_quant_multi(bine_comm_t comm, int ag_algo, int n, void *const *params8, void *const *scales8,
                         const void *const *src, const size_t *shard_counts, int sdtype, int fmt, void *stream);
+/* ---- MX-quantized gradient reduce-scatter of a bucket --------------------------------
+ * The quantized-gradient all-to-all of ZeRO++: sbufs[k] holds comm size shards
+ * of shard_counts[k] elements of sdtype (float, float16 or bfloat16), shard j
+ * the contribution to rank j's shard; rbufs[k] receives this rank's reduced
+ * shard, shard_counts[k] elements of rdtype.  The exchange carries 1 + 1/32
+ * bytes per element (FP8) or 1/2 + 1/32 (E2M1) where bine_reduce_scatter_multi
+ * carries 4 or 2.  With P = comm size and B = bine_mx_wire_bytes' block of the
+ * bucket, bit for bit this sequence, all on the caller's stream:
+ *   1. ONE set of bine_mx_quant_segments launches over the n * P (tensor,
+ *      destination) pairs: source sbufs[k] + j * shard_counts[k] elements, data
+ *      and scale bytes into tensor k's slots of block j of send_ws;
+ *   2. ONE bine_alltoall(comm, a2a_algo, send_ws, recv_ws, B, BINE_UINT8): block j
+ *      of recv_ws came from rank j;
+ *   3. bine_mx_sum_segments(n, P, recv_ws, B, rbufs, shard_counts, rdtype, fmt,
+ *      scale): rank 0's contribution first, then 1, 2, ... in binary32.
+ * Every value is quantized ONCE and never requantized on the way (no quantized
+ * ring or tree).  A rank's own shard is quantized like the others -- a
+ * deliberate choice: the result then does not depend on which rank owns a
+ * shard, every rank's shard of a tensor is the same function of the P inputs.
+ * A block of 32 with an inf or a NaN on any rank is 32 quiet NaNs on its owner.
+ * Every shard count must be a multiple of 32 (blocks never straddle ranks).
+ * send_ws and recv_ws: P * B bytes each (ws_bytes: what each holds), 16-B
+ * aligned, disjoint from each other and from every buffer; both are
+ * overwritten.  rbufs[k] may overlap sbufs[k]: step 1 has read every source
+ * before step 3 writes.  The kernels of 1 and 3 are ordinary launches, never
+ * captured; with graph mode on the all-to-all replays as any call on those
+ * addresses.  With n = 0 or every shard count 0 the call succeeds and writes
+ * nothing.  Refusals, before any exchange and any HIP call, in this order:
+ * sdtype, rdtype or fmt; n < 0 or n > BINE_MULTI_MAX; sbufs, rbufs or
+ * shard_counts NULL with n > 0; a NULL buffer with a non-zero count; a source
+ * or destination not aligned to its element size; a shard count not a multiple
+ * of 32, or above INT_MAX; unless every count is 0, send_ws or recv_ws NULL or
+ * not 16-B aligned, the two overlapping within ws_bytes, ws_bytes < P * B (P
+ * = 1 where comm is NULL) (all BINE_ERR_ARG); a2a_algo not BINE_A2A_BINE
+ * (BINE_ERR_UNSUPPORTED); comm == NULL (BINE_ERR_ARG); a communicator of more
+ * than BINE_MX_SUM_MAX_STREAMS ranks (BINE_ERR_UNSUPPORTED).  Where alltoall_bine has
+ * no plan for the communicator's P, step 2's status is returned.  Not
+ * provided: MXFP6, an error-feedback residual, a hierarchical (two-hop) form,
+ * a direct all-peers exchange, the sum fused into k_adamw_segs. */
+int bine_mx_reduce_scatter_multi(bine_comm_t comm, int a2a_algo, int n, const void *const *sbufs,
+                                 void *const *rbufs, const size_t *shard_counts, int sdtype, int rdtype, int fmt,
+                                 double scale, void *send_ws, void *recv_ws, size_t ws_bytes, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -1426,6 +1528,15 @@ int bine_loopback_run_quant_multi(bine_comm_t *comms, int nranks, int amax_algo,
 int bine_loopback_run_mx_quant_multi(bine_comm_t *comms, int nranks, int ag_algo, int n, void *const *params8,
                                      void *const *scales8, const void *const *src, const size_t *shard_counts,
                                      int sdtype, int fmt, int *statuses);
+/* bine_mx_reduce_scatter_multi on every virtual rank: sbufs and rbufs hold
+ * nranks * n entries, rank r's tensor k at [r * n + k]; shard_counts n entries
+ * (every rank's); send_ws and recv_ws one pointer per rank, ws_bytes each.  The
+ * refusals that need no communicator are made before any thread starts. */
+int bine_loopback_run_mx_reduce_scatter_multi(bine_comm_t *comms, int nranks, int a2a_algo, int n,
+                                              const void *const *sbufs, void *const *rbufs,
+                                              const size_t *shard_counts, int sdtype, int rdtype, int fmt,
+                                              double scale, void *const *send_ws, void *const *recv_ws,
+                                              size_t ws_bytes, int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

@@ -59,6 +59,13 @@ and ``adamw_segments_dyn`` / ``adamw_multi_dyn`` take everything from it, storin
 nothing on a skipped step: no host decision, no synchronization.
 ``step_update_host`` is the update's host twin, ``step_state_read`` the state as
 a dict (it synchronizes).
+
+MX-quantized gradient reduce-scatter: ``mx_reduce_scatter_multi`` quantizes
+every shard of a bucket once to OCP MX blocks (32 elements per E8M0 scale byte,
+e4m3 / e5m2 / e2m1 data), moves them in ONE all-to-all and leaves every rank
+the float32-accumulated sum of its shards; ``mx_sum_segments`` is the receiving
+half on its own (up to 16 wire blocks decoded and added in order),
+``mx_wire_bytes`` and ``plan_mx_sum`` the host views of its layout and launches.
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

@@ -1291,6 +1291,120 @@ def loopback_mx_quant_multi(comms, ag_algo, params8, scales8, src, fmt, sdtype=N
     return rc, list(st)
 
 
+# ---- MX-quantized gradient reduce-scatter of a bucket ----------------------------------------
+
+def mx_wire_bytes(shard_counts: Sequence[int], fmt):
+    """(D, B) of a bucket's wire block (bine_mx_wire_bytes, host only): D data
+    bytes -- tensor k's at the prefix sum of mx_dbytes before k -- then the
+    scale bytes, one per 32 elements in tensor order, B = D + S rounded up to a
+    multiple of 16.  Every count a multiple of 32."""
+    n = len(shard_counts)
+    d, b = ctypes.c_size_t(), ctypes.c_size_t()
+    check(lib().bine_mx_wire_bytes(n, (ctypes.c_size_t * max(n, 1))(*shard_counts), _mx(fmt), ctypes.byref(d),
+                                   ctypes.byref(b)), "bine_mx_wire_bytes")
+    return d.value, b.value
+
+
+def plan_mx_sum(dst: Sequence[int], counts: Sequence[int], ddtype, fmt):
+    """The launches of mx_sum_segments for these destination addresses
+    (bine_plan_mx_sum, host only): plan_mx's records, body 0 = vector (dst
+    16-B aligned), 1 = element."""
+    n = len(counts)
+    if len(dst) != n:
+        raise ValueError("plan_mx_sum: dst and counts differ in length")
+    args = (n, (ctypes.c_uint64 * max(n, 1))(*dst), (ctypes.c_size_t * max(n, 1))(*counts), _adamw_dtype(ddtype, ()),
+            _mx(fmt))
+    cap = lib().bine_plan_mx_sum(*args, None, 0)
+    if cap < 0:
+        raise BineError(int(-cap), "bine_plan_mx_sum")
+    out = (ctypes.c_uint64 * (5 * max(cap, 1)))()
+    lib().bine_plan_mx_sum(*args, out, cap)
+    return [tuple(out[5 * t:5 * t + 5]) for t in range(cap)]
+
+
+def mx_sum_segments(packed, nstreams: int, block_bytes: int, dst, fmt, scale: float = 1.0, ddtype=None, counts=None,
+                    stream=None) -> None:
+    """dst[k][i] = narrow((d_0 + d_1 + ... in that order, float32) * scale) over
+    the nstreams (1 .. 16) wire blocks of `packed`, block j at packed + j *
+    block_bytes in mx_wire_bytes' layout, d_j = decode(data) * 2^(S - 127)
+    exactly (bine_mx_sum_segments).  A block of 32 whose scale byte is 0xFF in
+    any stream gives quiet NaNs.  packed: uint8, 16-B aligned."""
+    c = _norm_counts("mx_sum_segments", dst, counts)
+    check(lib().bine_mx_sum_segments(len(dst), int(nstreams), _ptr(packed), int(block_bytes), _ptrs(dst), c,
+                                     _adamw_dtype(ddtype, dst), _mx(fmt), float(scale), _stream(stream, None)),
+          "bine_mx_sum_segments")
+
+
+def _mx_rs_scale(op: str, scale, comm: Comm) -> float:
+    op, scale = _scaled(op, scale, comm)
+    if op != "sum":
+        raise ValueError('mx_reduce_scatter_multi: op is "sum" or "avg"')
+    return 1.0 if scale is None else float(scale)
+
+
+def mx_reduce_scatter_multi(sbufs, rbufs, fmt, comm: Comm, op: str = "sum", scale=None, a2a_algo="bine", sdtype=None,
+                            rdtype=None, shard_counts=None, send_ws=None, recv_ws=None, stream=None):
+    """bine_mx_reduce_scatter_multi: sbufs[k] holds comm.size shards of
+    shard_counts[k] elements (float / float16 / bfloat16), rbufs[k] receives
+    this rank's shard of their sum -- every shard quantized once to MX blocks
+    (this rank's own too), ONE alltoall of comm.size blocks of mx_wire_bytes'
+    B bytes, then mx_sum_segments: the contributions decoded and added in rank
+    order in float32, times scale (op="avg": 1 / comm.size), rounded once into
+    rbufs' type.  Every shard count a multiple of 32; rbufs[k] may overlap
+    sbufs[k].  send_ws / recv_ws: comm.size * B uint8 each, 16-B aligned
+    (allocated when None).  Returns (send_ws, recv_ws)."""
+    if sbufs is None or len(sbufs) != len(rbufs):
+        raise ValueError("mx_reduce_scatter_multi: sbufs and rbufs differ in length")
+    s = _mx_rs_scale(op, scale, comm)
+    if shard_counts is None:
+        shard_counts = [b.numel() for b in rbufs]
+    c = _norm_counts("mx_reduce_scatter_multi", rbufs, shard_counts)
+    need = comm.size * mx_wire_bytes(list(shard_counts), fmt)[1]
+    if send_ws is None or recv_ws is None:
+        import torch
+        dev = _dev_of(list(rbufs) + list(sbufs))
+        send_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev) if send_ws is None else send_ws
+        recv_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev) if recv_ws is None else recv_ws
+    ws_bytes = min(send_ws.numel(), recv_ws.numel()) if hasattr(send_ws, "numel") and hasattr(recv_ws, "numel") else need
+    check(lib().bine_mx_reduce_scatter_multi(comm.handle, _algo("alltoall", a2a_algo), len(rbufs), _ptrs(sbufs),
+                                             _ptrs(rbufs), c, _adamw_dtype(sdtype, sbufs), _adamw_dtype(rdtype, rbufs),
+                                             _mx(fmt), s, _ptr(send_ws), _ptr(recv_ws), ws_bytes,
+                                             _stream(stream, comm)), f"mx_reduce_scatter_multi ({a2a_algo})")
+    return send_ws, recv_ws
+
+
+def loopback_mx_reduce_scatter_multi(comms, sbufs, rbufs, fmt, op: str = "sum", scale=None, a2a_algo="bine",
+                                     sdtype=None, rdtype=None, shard_counts=None, send_ws=None, recv_ws=None):
+    """mx_reduce_scatter_multi on every virtual rank: sbufs and rbufs one list
+    of tensors per rank, shard_counts one list for all ranks (None: rank 0's
+    rbufs' numel()), send_ws / recv_ws one uint8 buffer per rank (allocated
+    when None).  Returns (status, per-rank statuses)."""
+    P = len(comms)
+    n = len(rbufs[0])
+    if any(len(x) != P for x in (sbufs, rbufs)) or any(len(r) != n for x in (sbufs, rbufs) for r in x):
+        raise ValueError("loopback_mx_reduce_scatter_multi: the ranks' lists differ in length")
+    s = _mx_rs_scale(op, scale, comms[0])
+    if shard_counts is None:
+        shard_counts = [t.numel() for t in rbufs[0]]
+    need = P * mx_wire_bytes(list(shard_counts), fmt)[1]
+    flat = lambda x: [t for r in x for t in r]  # noqa: E731
+    if send_ws is None or recv_ws is None:
+        import torch
+        dev = _dev_of(flat(rbufs) + flat(sbufs))
+        mk = lambda: [torch.empty(max(need, 16), dtype=torch.uint8, device=dev) for _ in range(P)]  # noqa: E731
+        send_ws = mk() if send_ws is None else send_ws
+        recv_ws = mk() if recv_ws is None else recv_ws
+    ws = [w.numel() for w in list(send_ws) + list(recv_ws) if hasattr(w, "numel")]
+    ws_bytes = min(ws) if ws else need
+    st = (ctypes.c_int * P)()
+    hs = (ctypes.c_void_p * P)(*[c.handle.value for c in comms])
+    rc = lib().bine_loopback_run_mx_reduce_scatter_multi(
+        hs, P, _algo("alltoall", a2a_algo), n, _ptrs(flat(sbufs)), _ptrs(flat(rbufs)),
+        (ctypes.c_size_t * max(n, 1))(*shard_counts), _adamw_dtype(sdtype, flat(sbufs)),
+        _adamw_dtype(rdtype, flat(rbufs)), _mx(fmt), s, _ptrs(send_ws), _ptrs(recv_ws), ws_bytes, st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -1689,7 +1803,8 @@ __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fus
            "amax_segments", "fp8_scales", "fp8_scale_host", "quant_segments", "dequant_segments", "plan_quant",
            "quant_multi", "loopback_quant_multi",
            "mx_dbytes", "mx_scale_host", "plan_mx", "mx_quant_segments", "mx_dequant_segments", "mx_quant_multi",
-           "loopback_mx_quant_multi",
+           "loopback_mx_quant_multi", "mx_wire_bytes", "plan_mx_sum", "mx_sum_segments", "mx_reduce_scatter_multi",
+           "loopback_mx_reduce_scatter_multi",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

@@ -551,6 +551,32 @@ int launch_mx_quant_segments_h16(const std::vector<MxLaunch> &ls, const void *co
                                  void *const *scl8, const size_t *counts, int sdtype, int fmt, void *stream);
 int launch_mx_dequant_segments_h16(const std::vector<MxLaunch> &ls, const void *const *src8, const void *const *scl8,
                                    void *const *dst, const size_t *counts, int ddtype, int fmt, void *stream);
+// The wire layout of a bucket (bine_mx_wire_bytes): per tensor its data offset
+// in a block and its scale offset (D + the prefix sum of counts / 32), then D
+// and B.  BINE_ERR_ARG for fmt, n < 0, counts NULL with n > 0, a count not a
+// multiple of 32, a sum that overflows.  off: 2n entries (data, then scale), or NULL.
+int mx_wire_layout(int n, const size_t *counts, int fmt, std::vector<uint64_t> *off, uint64_t *data_bytes,
+                   uint64_t *block_bytes);
+// k_mx_sum_segs: plan_mx_launches' table over the DESTINATION (the same tiles,
+// whole blocks from the segment's first element) with the body flag of dst
+// alone -- a block's data offsets are multiples of 16 and `packed` is 16-B
+// aligned -- then the counts' multiples of 32.
+constexpr int kMxSumMaxStreams = BINE_MX_SUM_MAX_STREAMS;
+int plan_mx_sum_launches(int n, const uint64_t *dst, const size_t *counts, int ddtype, int fmt,
+                         std::vector<MxLaunch> &out);
+// Every check of bine_mx_sum_segments in the header's order, nothing launched;
+// ls: the launches, off: mx_wire_layout's offsets, where given.
+int mx_sum_args(int n, int nstreams, const void *packed, size_t block_bytes, void *const *dst, const size_t *counts,
+                int ddtype, int fmt, const char **why, std::vector<MxLaunch> *ls, std::vector<uint64_t> *off);
+// bine_mx_reduce_scatter_multi's checks that need no communicator and no
+// algorithm id, in the header's order, for a communicator of P ranks; *block =
+// B (0: every count is 0, the workspaces were not looked at)
+int mx_rs_args(int P, int n, const void *const *sbufs, void *const *rbufs, const size_t *shard_counts, int sdtype,
+               int rdtype, int fmt, const void *send_ws, const void *recv_ws, size_t ws_bytes, const char **why,
+               uint64_t *block, std::vector<uint64_t> *off);
+int launch_mx_sum_segments_h16(const std::vector<MxLaunch> &ls, const std::vector<uint64_t> &off, int n, int nstreams,
+                               const void *packed, size_t block_bytes, void *const *dst, const size_t *counts,
+                               int ddtype, int fmt, float scale, void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -2977,6 +2977,158 @@ int launch_mx_dequant_segments_h16(const std::vector<MxLaunch> &ls, const void *
                                    void *const *dst, const size_t *counts, int ddtype, int fmt, void *stream) {
   return mx_issue<true>(ls, dst, src8, scl8, counts, ddtype, fmt, stream);
 }
+
+// ----------------------------------------------------------------------------
+// The ordered binary32 sum of MX wire blocks (bine_mx_sum_segments, bine_amd.h):
+// k_mx_sum_segs.  TileTable's dispatch over plan_mx_sum_launches' table of the
+// DESTINATION, k_mx_segs' tiles (kBlock * kScaleU 16-B vectors of dst from the
+// segment's first element: whole blocks; every count is a multiple of 32, so
+// there is no short block).  Stream j of a slot is (packed + j * block) + its
+// data and scale offsets.  No LDS, no atomics, no barrier.
+
+// data code b of a block with scale byte S as binary32: decode(b) * 2^(S - 127),
+// exact (the header); a NaN byte and S = 0xFF give a quiet NaN
+template <int FMT>
+__device__ __forceinline__ float mx_value(uint32_t b, uint32_t S) {
+  const uint32_t r = mx_dequant1<float, FMT>(b, S);
+  float f;
+  __builtin_memcpy(&f, &r, 4);
+  return f;
+}
+// T's positive quiet NaN: what mx_dequant1 gives for S = 0xFF
+template <typename T>
+__device__ __forceinline__ uint_of<T> mx_qnan() {
+  return mx_dequant1<T, BINE_MX_E2M1>(0u, 0xffu);
+}
+
+struct MxSumSeg {
+  uint8_t *dst;
+  uint64_t doff, soff;  // the tensor's data and scale bytes in a block
+  uint64_t n;           // elements, a multiple of 32
+};
+struct MxSumSegs {
+  TileTable<kMxSegsPerLaunch> tab;
+  uint64_t elem[(kMxSegsPerLaunch + 63) / 64];  // bit s: slot s takes the element body
+  const uint8_t *packed;
+  uint64_t block;  // bytes from one stream to the next
+  uint32_t ns;     // streams, 1 .. kMxSumMaxStreams
+  float scale;
+  MxSumSeg s[kMxSegsPerLaunch];
+};
+static_assert(sizeof(MxSumSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+
+template <typename T, int FMT>
+__global__ __launch_bounds__(kBlock) void k_mx_sum_segs(MxSumSegs a) {
+  constexpr size_t V = 16 / sizeof(T);  // elements of one dst vector
+  constexpr size_t TV = (size_t)kBlock * kScaleU;
+  constexpr int BITS = FMT == BINE_MX_E2M1 ? 4 : 8;
+  constexpr int R = 128 / BITS;  // the elements of one 16-B data load: a lane's run
+  static_assert(TV * V % ((size_t)kBlock * R) == 0, "a tile is whole steps of kBlock runs");
+  const auto [k, wt] = a.tab.find(blockIdx.x);
+  T *dst = reinterpret_cast<T *>(a.s[k].dst);
+  const size_t n = a.s[k].n;
+  const bool elem = (a.elem[k >> 6] >> (k & 63)) & 1;
+  const uint8_t *dat = a.packed + a.s[k].doff, *scl = a.packed + a.s[k].soff;
+  const size_t block = a.block;
+  const uint32_t ns = a.ns;
+  const float sc = a.scale;
+  // the tile's elements [lo, hi): whole blocks
+  const size_t lo = (size_t)wt * TV * V;
+  const size_t hi = lo + TV * V < n ? lo + TV * V : n;
+  if (!elem) {
+#pragma unroll 1
+    for (size_t e0 = lo + (size_t)threadIdx.x * R; e0 < hi; e0 += (size_t)kBlock * R) {  // e0 + R <= hi: hi % 32 == 0
+      // every stream's load issued before the first use; j < ns is uniform
+      u32x4 x[kMxSumMaxStreams];
+      uint32_t S[kMxSumMaxStreams];
+#pragma unroll
+      for (int j = 0; j < kMxSumMaxStreams; j++)
+        if ((uint32_t)j < ns) {
+          x[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(dat + (size_t)j * block) + e0 / R);
+          S[j] = __builtin_nontemporal_load(scl + (size_t)j * block + e0 / kMxBlock);
+        }
+      float acc[R];
+      bool dead = false;  // the same in every lane of a block
+#pragma unroll
+      for (int j = 0; j < kMxSumMaxStreams; j++)
+        if ((uint32_t)j < ns) {
+          dead |= S[j] == 0xffu;
+#pragma unroll
+          for (int i = 0; i < R; i++) {
+            const float d = mx_value<FMT>((x[j][i * BITS / 32] >> (i * BITS % 32)) & ((1u << BITS) - 1), S[j]);
+            acc[i] = j ? acc[i] + d : d;
+          }
+        }
+#pragma unroll
+      for (int i = 0; i < R; i++) acc[i] = acc[i] * sc;
+      u32x4 *vo = reinterpret_cast<u32x4 *>(dst + e0);
+      const uint32_t q = mx_qnan<T>();
+#pragma unroll
+      for (int v = 0; v < R / (int)V; v++) {
+        u32x4 r;
+        if constexpr (sizeof(T) == 4) {
+          __builtin_memcpy(&r, acc + 4 * v, 16);
+          if (dead) r = u32x4{q, q, q, q};
+        } else {
+          W8 w;
+          __builtin_memcpy(&w.a, acc + 8 * v, 16);
+          __builtin_memcpy(&w.b, acc + 8 * v + 4, 16);
+          r = narrow16<T>(w);
+          if (dead) r = u32x4{q, q, q, q} * 0x10001u;
+        }
+        __builtin_nontemporal_store(r, vo + v);
+      }
+    }
+  } else {  // one element per lane, byte loads
+#pragma unroll 1
+    for (size_t i = lo + threadIdx.x; i < hi; i += kBlock) {
+      auto code = [&](uint32_t j) -> uint32_t {
+        const uint8_t *d8 = dat + (size_t)j * block;
+        return FMT == BINE_MX_E2M1 ? (d8[i >> 1] >> (4 * (i & 1))) & 15u : d8[i];
+      };
+      uint32_t S = scl[i / kMxBlock];
+      bool dead = S == 0xffu;
+      float acc = mx_value<FMT>(code(0), S);
+#pragma unroll 1
+      for (uint32_t j = 1; j < ns; j++) {
+        S = scl[(size_t)j * block + i / kMxBlock];
+        dead |= S == 0xffu;
+        acc = acc + mx_value<FMT>(code(j), S);
+      }
+      const T t = adamw_narrow<T>(acc * sc);
+      uint_of<T> r;
+      __builtin_memcpy(&r, &t, sizeof r);
+      __builtin_nontemporal_store(dead ? mx_qnan<T>() : r, reinterpret_cast<uint_of<T> *>(dst) + i);
+    }
+  }
+}
+
+int launch_mx_sum_segments_h16(const std::vector<MxLaunch> &ls, const std::vector<uint64_t> &off, int n, int nstreams,
+                               const void *packed, size_t block_bytes, void *const *dst, const size_t *counts,
+                               int ddtype, int fmt, float scale, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  return with_adamw_dtype(ddtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    for (const MxLaunch &L : ls) {
+      MxSumSegs a;
+      for (size_t w = 0; w < sizeof a.elem / sizeof a.elem[0]; w++) a.elem[w] = L.elem[w];
+      a.packed = (const uint8_t *)packed;
+      a.block = block_bytes;
+      a.ns = (uint32_t)nstreams;
+      a.scale = scale;
+      fill_segs(a, L, [&](int s) {
+        const int k = L.seg[s];
+        return MxSumSeg{(uint8_t *)dst[k], off[(size_t)k], off[(size_t)n + k], (uint64_t)counts[k]};
+      });
+      const dim3 grid(L.tile0[L.nseg]), blk(kBlock);
+      if (fmt == BINE_MX_E4M3) hipLaunchKernelGGL((k_mx_sum_segs<T, BINE_MX_E4M3>), grid, blk, 0, st, a);
+      else if (fmt == BINE_MX_E5M2) hipLaunchKernelGGL((k_mx_sum_segs<T, BINE_MX_E5M2>), grid, blk, 0, st, a);
+      else hipLaunchKernelGGL((k_mx_sum_segs<T, BINE_MX_E2M1>), grid, blk, 0, st, a);
+      if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+    }
+    return BINE_SUCCESS;
+  });
+}
 #endif  // BINE_OPSET == 2
 
 #if BINE_OPSET == 0

@@ -24,6 +24,11 @@
 //                                            flag per slot; the MX calls' refusals (mx_args, mx_multi_args)
 //                                            and bine_mx_scale_host, the host compilation of mx_scale_rule
 //                                            (tools/mx_check.cpp)
+//   plan_mx_sum_launches / bine_plan_mx_sum  k_mx_sum_segs: plan_mx_launches' table over the destination,
+//                                            the body flag dst's alone; the wire layout of a bucket
+//                                            (mx_wire_layout, bine_mx_wire_bytes) and the refusals of the
+//                                            sum and of the MX reduce-scatter (mx_sum_args, mx_rs_args;
+//                                            tools/mxrs_check.cpp)
 // Dynamic loss scaling keeps its host half here too:
 // bine_step_state_init, the refusals (step_update_args, adamw_dyn_args) and
 // bine_step_update_host, the host compilation of the statement k_step_update
@@ -388,7 +393,123 @@ int mx_multi_args(int n, void *const *params8, void *const *scales8, const void 
   return BINE_SUCCESS;
 }
 
+int mx_wire_layout(int n, const size_t *counts, int fmt, std::vector<uint64_t> *off, uint64_t *data_bytes,
+                   uint64_t *block_bytes) {
+  if (!mx_fmt_ok(fmt) || n < 0 || (n > 0 && !counts)) return BINE_ERR_ARG;
+  if (off) off->assign(2 * (size_t)n, 0);
+  uint64_t d = 0, s = 0;
+  for (int k = 0; k < n; k++) {
+    if (counts[k] % kMxBlock) return BINE_ERR_ARG;
+    if (off) (*off)[k] = d, (*off)[(size_t)n + k] = s;
+    // a multiple of 32: dbytes is a multiple of 16, and count + 1 does not wrap
+    if (__builtin_add_overflow(d, mx_dbytes(counts[k], fmt), &d) ||
+        __builtin_add_overflow(s, (uint64_t)counts[k] / kMxBlock, &s))
+      return BINE_ERR_ARG;
+  }
+  uint64_t t;
+  if (__builtin_add_overflow(d, s, &t) || __builtin_add_overflow(t, (uint64_t)15, &t)) return BINE_ERR_ARG;
+  if (off)
+    for (int k = 0; k < n; k++) (*off)[(size_t)n + k] += d;
+  if (data_bytes) *data_bytes = d;
+  if (block_bytes) *block_bytes = t & ~(uint64_t)15;
+  return BINE_SUCCESS;
+}
+
+int plan_mx_sum_launches(int n, const uint64_t *dst, const size_t *counts, int ddtype, int fmt,
+                         std::vector<MxLaunch> &out) {
+  // the byte side stands on a 16-B boundary in every block: mx_body is dst's alone
+  const std::vector<uint64_t> unit((size_t)(n > 0 ? n : 0), 16);
+  if (const int rc = plan_mx_launches(n, dst, unit.data(), unit.data(), counts, ddtype, fmt, out)) return rc;
+  for (int k = 0; k < n; k++)
+    if (counts[k] % kMxBlock) {
+      out.clear();
+      return BINE_ERR_ARG;
+    }
+  return BINE_SUCCESS;
+}
+
+int mx_sum_args(int n, int nstreams, const void *packed, size_t block_bytes, void *const *dst, const size_t *counts,
+                int ddtype, int fmt, const char **why, std::vector<MxLaunch> *ls, std::vector<uint64_t> *off) {
+  if (!adamw_esz(ddtype)) return refuse(why, "ddtype: float, float16 or bfloat16");
+  if (!mx_fmt_ok(fmt)) return refuse(why, "fmt: BINE_MX_E4M3, BINE_MX_E5M2 or BINE_MX_E2M1");
+  std::vector<uint64_t> a;
+  if (seg_list_addrs(n, counts, {dst}, a)) return refuse(why, "n outside [0, BINE_MULTI_MAX], or a NULL array");
+  std::vector<MxLaunch> local;
+  std::vector<MxLaunch> &L = ls ? *ls : local;
+  const std::vector<uint64_t> unit((size_t)n, 16);
+  if (plan_mx_launches(n, a.data(), unit.data(), unit.data(), counts, ddtype, fmt, L))
+    return refuse(why, "a NULL buffer with a non-zero count, or a destination not aligned to its element");
+  uint64_t D = 0, B = 0;
+  if (mx_wire_layout(n, counts, fmt, off, &D, &B)) {
+    L.clear();
+    return refuse(why, "a count not a multiple of 32, or the bucket's bytes overflow");
+  }
+  if (nstreams < 1 || nstreams > kMxSumMaxStreams) return refuse(why, "nstreams outside [1, 16]");
+  if (B == 0) return BINE_SUCCESS;
+  if (!packed || ((uintptr_t)packed & 15)) return refuse(why, "packed NULL or not 16-B aligned");
+  if (block_bytes % 16 || block_bytes < B)
+    return refuse(why, "block_bytes not a multiple of 16, or below the bucket's wire block");
+  return BINE_SUCCESS;
+}
+
+int mx_rs_args(int P, int n, const void *const *sbufs, void *const *rbufs, const size_t *shard_counts, int sdtype,
+               int rdtype, int fmt, const void *send_ws, const void *recv_ws, size_t ws_bytes, const char **why,
+               uint64_t *block, std::vector<uint64_t> *off) {
+  if (block) *block = 0;
+  const size_t ssz = adamw_esz(sdtype), rsz = adamw_esz(rdtype);
+  if (!ssz || !rsz) return refuse(why, "sdtype, rdtype: float, float16 or bfloat16");
+  if (!mx_fmt_ok(fmt)) return refuse(why, "fmt: BINE_MX_E4M3, BINE_MX_E5M2 or BINE_MX_E2M1");
+  std::vector<uint64_t> a;  // sbufs, rbufs
+  if (seg_list_addrs(n, shard_counts, {sbufs, rbufs}, a))
+    return refuse(why, "n outside [0, BINE_MULTI_MAX], or a NULL array");
+  for (int k = 0; k < n; k++)
+    if (shard_counts[k] && (!a[k] || !a[(size_t)n + k])) return refuse(why, "a NULL buffer with a non-zero count");
+  for (int k = 0; k < n; k++)
+    if (shard_counts[k] && (a[k] % ssz || a[(size_t)n + k] % rsz))
+      return refuse(why, "a source or destination not aligned to its element");
+  for (int k = 0; k < n; k++)
+    if (shard_counts[k] % kMxBlock || shard_counts[k] > (size_t)INT_MAX)
+      return refuse(why, "a shard count not a multiple of 32, or above INT_MAX");
+  uint64_t D = 0, B = 0;
+  if (mx_wire_layout(n, shard_counts, fmt, off, &D, &B)) return refuse(why, "the bucket's bytes overflow");
+  if (block) *block = B;
+  if (B == 0) return BINE_SUCCESS;
+  if (!send_ws || !recv_ws || ((uintptr_t)send_ws & 15) || ((uintptr_t)recv_ws & 15))
+    return refuse(why, "send_ws or recv_ws NULL or not 16-B aligned");
+  const uint64_t s0 = (uint64_t)(uintptr_t)send_ws, r0 = (uint64_t)(uintptr_t)recv_ws;
+  if (s0 < r0 ? r0 - s0 < ws_bytes : s0 - r0 < ws_bytes) return refuse(why, "send_ws and recv_ws overlap");
+  if (ws_bytes / (uint64_t)(P > 0 ? P : 1) < B) return refuse(why, "ws_bytes below comm size * block bytes");
+  return BINE_SUCCESS;
+}
+
 }  // namespace bine
+
+extern "C" int bine_mx_wire_bytes(int n, const size_t *shard_counts, int fmt, size_t *data_bytes,
+                                  size_t *block_bytes) {
+  if (!data_bytes || !block_bytes) return BINE_ERR_ARG;
+  uint64_t D = 0, B = 0;
+  if (const int rc = bine::mx_wire_layout(n, shard_counts, fmt, nullptr, &D, &B)) return rc;
+  *data_bytes = (size_t)D, *block_bytes = (size_t)B;
+  return BINE_SUCCESS;
+}
+
+extern "C" int64_t bine_plan_mx_sum(int n, const uint64_t *dst, const size_t *counts, int ddtype, int fmt,
+                                    uint64_t *out, int64_t cap) {
+  std::vector<bine::MxLaunch> ls;
+  const int rc = bine::plan_mx_sum_launches(n, dst, counts, ddtype, fmt, ls);
+  if (rc) return -(int64_t)rc;
+  int64_t nt = 0;
+  for (size_t l = 0; l < ls.size(); l++) {
+    const bine::MxLaunch &L = ls[l];
+    for (int s = 0; s < L.nseg; s++, nt++)
+      if (out && nt < cap) {
+        uint64_t *e = out + 5 * nt;
+        e[0] = l, e[1] = (uint64_t)L.seg[s], e[2] = L.tile0[s], e[3] = L.tile0[s + 1] - L.tile0[s];
+        e[4] = (L.elem[s >> 6] >> (s & 63)) & 1;
+      }
+  }
+  return nt;
+}
 
 extern "C" int bine_fp8_scale_host(uint32_t amax_bits, int fmt, float *scale, float *inv) {
   if (!bine::fp8_fmt_ok(fmt) || !scale || !inv) return BINE_ERR_ARG;
