@@ -828,6 +828,77 @@ int bine_mx_sum_segments(int n, int nstreams, const void *packed, size_t block_b
                          const size_t *counts, int ddtype, int fmt, double scale, void *stream);
 int64_t bine_plan_mx_sum(int n, const uint64_t *dst, const size_t *counts, int ddtype, int fmt, uint64_t *out,
                          int64_t cap);
+/* ---- MX quantization with an error-feedback residual ----------------------------------
+ * The sending side of a quantized gradient exchange that keeps what it could not
+ * send (bine_mx_reduce_scatter_multi_ef, below with the collectives): the part of
+ * a value the format dropped is stored and added to the next call's value before
+ * that one is quantized, so the error of a coordinate does not repeat step after
+ * step -- the mean of what is sent converges to the mean of what was given.
+ *
+ * bine_mx_quant_ef_segments: src, dst8, scl8, blocks, dbytes and formats as in
+ * bine_mx_quant_segments, short last blocks as there; res[k] holds counts[k]
+ * binary32 values, 4-byte aligned, read and overwritten in place.  Per element,
+ * with x the source element and r its residual:
+ *   v  = widen(x) + r               one binary32 addition, nearest even
+ *   A, S                            mx_scale_rule over the block's v (not x)
+ *   S == 0xFF                       every data byte (nibble) of the block is 0 and
+ *                                   every residual of the block is stored as +0.0
+ *   else  q  = bine_mx_quant_segments' code for v under S: the same multiply,
+ *              clamp, nearest-even rounding and kept sign of zero
+ *         d  = decode(q) * 2^(S - 127)   bine_mx_dequant_segments' value into
+ *              float: one binary32 multiplication, exact
+ *         r' = v - d                one binary32 subtraction
+ * S = 0xFF covers an infinity or a NaN in x, a NaN in r and an x + r that
+ * overflows.  The zero residual is deliberate: the loss scaler drops such a
+ * step, and a residual that could hold a NaN would poison every later step of
+ * that block.
+ * What follows (tests/test_mxef.py proves it on every 16-bit pattern):
+ *   - the subtraction is exact: d is v rounded to a coarser grid that holds 0,
+ *     or FMAX * 2^(S - 127) between 0 and v, so |v - d| <= |v|, and d is a
+ *     multiple of ulp(v) -- in the format's subnormal range, under the clamp,
+ *     and at S = 0 with binary32 subnormals too (where |y| < 2^-126 the code is
+ *     a zero and r' = v).  No corner was found where it rounds;
+ *   - therefore widen(x) + r = d + r' up to the single rounding of the
+ *     addition: nothing else is lost;
+ *   - |r'| <= E_fmt * 2^(S - 127), E_fmt = 64 / 8192 / 2 (the clamp's 512 -> 448
+ *     case gives the 64);
+ *   - with every residual +0.0 the data and scale bytes are those of
+ *     bine_mx_quant_segments, except that an element -0 becomes +0 (-0 + +0 =
+ *     +0).
+ * Mechanism: k_mx_ef_segs over bine_mx_quant_segments' tile table of the SOURCE
+ * (32 KiB tiles from the segment's first element, at least one workgroup per
+ * non-empty segment), BINE_MX_EF_SEGS_PER_LAUNCH descriptors (four pointers and
+ * a count: 40 bytes, so 92 and not 112 fit HIP's 4 KiB of by-value arguments)
+ * per launch.  A segment whose source is 16-B aligned, whose dst8 is aligned as
+ * bine_mx_quant_segments' vector body requires and whose res is 16-B aligned
+ * takes the vector body: per source vector a lane loads one (float) or two
+ * (16-bit) 16-B residual vectors, all loads of a full tile issued before the
+ * first use, adds, agrees on A with the 8 (float) or 4 (16-bit) lanes of its
+ * block, encodes, decodes, subtracts and stores the data word, the residual
+ * vector(s) and one scale byte per block; every access of a full tile is
+ * non-temporal.  The final short block, and every other segment, takes the
+ * element body: one element per lane, 32 lanes a block, byte stores, the same
+ * bits.  No LDS, no atomics, no barrier.  One pass: the gradient is read once,
+ * the bytes written once (bine_mx_quant_segments, bine_mx_dequant_segments and
+ * a subtraction would read the gradient twice and write the bytes twice).
+ * BINE_ERR_ARG, before any HIP call, in this order: sdtype or fmt; n < 0 or n >
+ * BINE_MULTI_MAX; src, res, dst8, scl8 or counts NULL with n > 0; a NULL buffer
+ * with a non-zero count; a source not aligned to its element size; a residual
+ * not 4-byte aligned.  Ranges must not overlap (not checked).
+ *
+ * bine_plan_mx_ef (host only): the launches bine_mx_quant_ef_segments issues for
+ * these addresses, bine_plan_mx's 5-word records; body 1 (element) where the
+ * source or res is not 16-B aligned or data8 is not on the boundary
+ * bine_mx_quant_segments' vector body requires.
+ * Not provided: a 16-bit residual; rescaling the residual when the loss scale
+ * changes (apply bine_scale to it); skipping the residual update of a step the
+ * scaler drops. */
+#define BINE_MX_EF_SEGS_PER_LAUNCH 92
+int bine_mx_quant_ef_segments(int n, const void *const *src, void *const *res, void *const *dst8,
+                              void *const *scl8, const size_t *counts, int sdtype, int fmt, void *stream);
+int64_t bine_plan_mx_ef(int n, const uint64_t *src, const uint64_t *res, const uint64_t *data8,
+                        const uint64_t *scl8, const size_t *counts, int dtype, int fmt, uint64_t *out,
+                        int64_t cap);
 /* Order-independent 64-bit digest of a buffer: sum over i of
  * mix64(bits(x[i]) + i * 0x9E3779B97F4A7C15) mod 2^64 (bits zero-extended).
  * Result written to *out (host pointer) after an internal synchronize. */
@@ -1403,11 +1474,27 @@ int bine_mx_quant_multi(bine_comm_t comm, int ag_algo, int n, void *const *param
  * (BINE_ERR_UNSUPPORTED); comm == NULL (BINE_ERR_ARG); a communicator of more
  * than BINE_MX_SUM_MAX_STREAMS ranks (BINE_ERR_UNSUPPORTED).  Where alltoall_bine has
  * no plan for the communicator's P, step 2's status is returned.  Not
- * provided: MXFP6, an error-feedback residual, a hierarchical (two-hop) form,
- * a direct all-peers exchange, the sum fused into k_adamw_segs. */
+ * provided: MXFP6, a hierarchical (two-hop) form, a direct all-peers exchange,
+ * the sum fused into k_adamw_segs. */
 int bine_mx_reduce_scatter_multi(bine_comm_t comm, int a2a_algo, int n, const void *const *sbufs,
                                  void *const *rbufs, const size_t *shard_counts, int sdtype, int rdtype, int fmt,
                                  double scale, void *send_ws, void *recv_ws, size_t ws_bytes, void *stream);
+/* bine_mx_reduce_scatter_multi with an error-feedback residual: step 1 is ONE set
+ * of bine_mx_quant_ef_segments launches over the n * P (tensor, destination)
+ * pairs -- res[k] holds P * shard_counts[k] binary32 values laid out as
+ * sbufs[k], 4-byte aligned, read and overwritten -- and steps 2 and 3 are the
+ * plain call's: one bine_alltoall, then bine_mx_sum_segments.  What a rank
+ * could not send in this call it adds to its contribution in the next.
+ * rbufs[k] may overlap sbufs[k] but not res[k].  A block with an inf or a NaN
+ * in x + r is 32 quiet NaNs on its owner and leaves 32 zero residuals on the
+ * sender.  Refusals: the plain call's, in its order, with res beside sbufs
+ * (the NULL array, the NULL buffer with a non-zero count, the 4-byte
+ * alignment).  Not provided: what bine_mx_quant_ef_segments names, and what the
+ * plain call names. */
+int bine_mx_reduce_scatter_multi_ef(bine_comm_t comm, int a2a_algo, int n, const void *const *sbufs,
+                                    void *const *res, void *const *rbufs, const size_t *shard_counts, int sdtype,
+                                    int rdtype, int fmt, double scale, void *send_ws, void *recv_ws,
+                                    size_t ws_bytes, void *stream);
 /* reduce_* (libbine.h:64-65).  rbuf is only read on `root` (may be NULL elsewhere). */
 int bine_reduce(bine_comm_t comm, int algo, const void *sbuf, void *rbuf, size_t count,
                 int dtype, int op, int root, void *stream);
@@ -1537,6 +1624,13 @@ int bine_loopback_run_mx_reduce_scatter_multi(bine_comm_t *comms, int nranks, in
                                               const size_t *shard_counts, int sdtype, int rdtype, int fmt,
                                               double scale, void *const *send_ws, void *const *recv_ws,
                                               size_t ws_bytes, int *statuses);
+/* bine_mx_reduce_scatter_multi_ef on every virtual rank: the plain driver's
+ * arguments plus res, nranks * n entries, rank r's tensor k at [r * n + k] */
+int bine_loopback_run_mx_reduce_scatter_multi_ef(bine_comm_t *comms, int nranks, int a2a_algo, int n,
+                                                 const void *const *sbufs, void *const *res, void *const *rbufs,
+                                                 const size_t *shard_counts, int sdtype, int rdtype, int fmt,
+                                                 double scale, void *const *send_ws, void *const *recv_ws,
+                                                 size_t ws_bytes, int *statuses);
 int bine_loopback_run_reduce(bine_comm_t *comms, int nranks, int algo,
                              const void *const *sbufs, void *const *rbufs, size_t count,
                              int dtype, int op, int root, int *statuses);

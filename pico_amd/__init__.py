@@ -66,6 +66,11 @@ e4m3 / e5m2 / e2m1 data), moves them in ONE all-to-all and leaves every rank
 the float32-accumulated sum of its shards; ``mx_sum_segments`` is the receiving
 half on its own (up to 16 wire blocks decoded and added in order),
 ``mx_wire_bytes`` and ``plan_mx_sum`` the host views of its layout and launches.
+``mx_reduce_scatter_multi_ef`` is the same exchange with an error-feedback
+residual: ``mx_quant_ef_segments`` quantizes gradient + residual in one pass and
+stores what the format dropped back into the residual (float32, one per
+element), so the error of a coordinate is sent with a later step, not lost;
+``plan_mx_ef`` is the host view of its launches.
 """
 from ._lib import ALGOS, DTYPES, EXT_DTYPES, OPS, BineError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

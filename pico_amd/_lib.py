@@ -88,6 +88,7 @@ MX_FORMATS = {"e4m3": 0, "e5m2": 1, "e2m1": 2}
 MX_EMAX = {"e4m3": 8, "e5m2": 15, "e2m1": 2}
 MX_SEGS_PER_LAUNCH = 112
 MX_SUM_MAX_STREAMS = 16       # BINE_MX_SUM_MAX_STREAMS: the blocks one bine_mx_sum_segments adds
+MX_EF_SEGS_PER_LAUNCH = 92    # BINE_MX_EF_SEGS_PER_LAUNCH: 40-byte descriptors within 4 KiB of kernel arguments
 
 
 # the step state of bine_step_update (BINE_STEP_STATE_BYTES: 8 doubles, 8 floats)
@@ -244,6 +245,11 @@ def lib():
         "bine_mx_reduce_scatter_multi": ([vp, i, i, vp, vp, vp, i, i, i, ctypes.c_double, vp, vp, sz, vp], i),
         "bine_loopback_run_mx_reduce_scatter_multi":
             ([vp, i, i, i, vp, vp, vp, i, i, i, ctypes.c_double, vp, vp, sz, vp], i),
+        "bine_mx_quant_ef_segments": ([i, vp, vp, vp, vp, vp, i, i, vp], i),
+        "bine_plan_mx_ef": ([i, vp, vp, vp, vp, vp, i, i, vp, ctypes.c_int64], ctypes.c_int64),
+        "bine_mx_reduce_scatter_multi_ef": ([vp, i, i, vp, vp, vp, vp, i, i, i, ctypes.c_double, vp, vp, sz, vp], i),
+        "bine_loopback_run_mx_reduce_scatter_multi_ef":
+            ([vp, i, i, i, vp, vp, vp, vp, i, i, i, ctypes.c_double, vp, vp, sz, vp], i),
         "bine_loopback_run_allgather": ([vp, i, i, vp, vp, sz, i, vp], i),
         "bine_bcast": ([vp, i, vp, sz, i, i, vp], i),
         "bine_loopback_run_bcast": ([vp, i, i, vp, sz, i, i, vp], i),

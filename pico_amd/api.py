@@ -1405,6 +1405,102 @@ def loopback_mx_reduce_scatter_multi(comms, sbufs, rbufs, fmt, op: str = "sum", 
     return rc, list(st)
 
 
+# ---- the same with an error-feedback residual -------------------------------------------------
+
+def plan_mx_ef(src: Sequence[int], res: Sequence[int], data8: Sequence[int], scl8: Sequence[int],
+               counts: Sequence[int], dtype, fmt):
+    """The launches of mx_quant_ef_segments for these source, residual, data
+    and scale addresses (bine_plan_mx_ef, host only): plan_mx's records, at most
+    MX_EF_SEGS_PER_LAUNCH segments per launch, body 0 = vector (source and
+    residual 16-B aligned, data8 as plan_mx asks), 1 = element."""
+    n = len(counts)
+    if len(src) != n or len(res) != n or len(data8) != n or len(scl8) != n:
+        raise ValueError("plan_mx_ef: the address lists and counts differ in length")
+    arr = lambda a: (ctypes.c_uint64 * max(n, 1))(*a)  # noqa: E731
+    args = (n, arr(src), arr(res), arr(data8), arr(scl8), (ctypes.c_size_t * max(n, 1))(*counts),
+            _adamw_dtype(dtype, ()), _mx(fmt))
+    cap = lib().bine_plan_mx_ef(*args, None, 0)
+    if cap < 0:
+        raise BineError(int(-cap), "bine_plan_mx_ef")
+    out = (ctypes.c_uint64 * (5 * max(cap, 1)))()
+    lib().bine_plan_mx_ef(*args, out, cap)
+    return [tuple(out[5 * t:5 * t + 5]) for t in range(cap)]
+
+
+def mx_quant_ef_segments(src, res, dst8, scl8, fmt, sdtype=None, counts=None, stream=None) -> None:
+    """mx_quant_segments with an error-feedback residual
+    (bine_mx_quant_ef_segments): v = widen(src) + res in float32 is what gets
+    quantized -- scale bytes from v's blocks, data as mx_quant_segments gives
+    for v -- and res is overwritten with v - decode * 2^(S - 127), exactly what
+    the format dropped.  A block with an inf or a NaN in v gets S = 0xFF, zero
+    data and zero residuals.  res[k]: float32, one per element of src[k]."""
+    if len(src) != len(res) or len(src) != len(dst8) or len(src) != len(scl8):
+        raise ValueError("mx_quant_ef_segments: src, res, dst8 and scl8 differ in length")
+    c = _norm_counts("mx_quant_ef_segments", src, counts)
+    check(lib().bine_mx_quant_ef_segments(len(src), _ptrs(src), _ptrs(res), _ptrs(dst8), _ptrs(scl8), c,
+                                          _adamw_dtype(sdtype, src), _mx(fmt), _stream(stream, None)),
+          "bine_mx_quant_ef_segments")
+
+
+def mx_reduce_scatter_multi_ef(sbufs, res, rbufs, fmt, comm: Comm, op: str = "sum", scale=None, a2a_algo="bine",
+                               sdtype=None, rdtype=None, shard_counts=None, send_ws=None, recv_ws=None, stream=None):
+    """bine_mx_reduce_scatter_multi_ef: mx_reduce_scatter_multi whose first step
+    is mx_quant_ef_segments.  res[k]: float32, comm.size * shard_counts[k]
+    values laid out as sbufs[k], read and overwritten -- what this rank could
+    not send now it adds to its contribution in the next call.  rbufs[k] may
+    overlap sbufs[k] but not res[k].  Returns (send_ws, recv_ws)."""
+    if sbufs is None or res is None or len(sbufs) != len(rbufs) or len(res) != len(rbufs):
+        raise ValueError("mx_reduce_scatter_multi_ef: sbufs, res and rbufs differ in length")
+    s = _mx_rs_scale(op, scale, comm)
+    if shard_counts is None:
+        shard_counts = [b.numel() for b in rbufs]
+    c = _norm_counts("mx_reduce_scatter_multi_ef", rbufs, shard_counts)
+    need = comm.size * mx_wire_bytes(list(shard_counts), fmt)[1]
+    if send_ws is None or recv_ws is None:
+        import torch
+        dev = _dev_of(list(rbufs) + list(sbufs))
+        send_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev) if send_ws is None else send_ws
+        recv_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev) if recv_ws is None else recv_ws
+    ws_bytes = min(send_ws.numel(), recv_ws.numel()) if hasattr(send_ws, "numel") and hasattr(recv_ws, "numel") else need
+    check(lib().bine_mx_reduce_scatter_multi_ef(comm.handle, _algo("alltoall", a2a_algo), len(rbufs), _ptrs(sbufs),
+                                                _ptrs(res), _ptrs(rbufs), c, _adamw_dtype(sdtype, sbufs),
+                                                _adamw_dtype(rdtype, rbufs), _mx(fmt), s, _ptr(send_ws), _ptr(recv_ws),
+                                                ws_bytes, _stream(stream, comm)),
+          f"mx_reduce_scatter_multi_ef ({a2a_algo})")
+    return send_ws, recv_ws
+
+
+def loopback_mx_reduce_scatter_multi_ef(comms, sbufs, res, rbufs, fmt, op: str = "sum", scale=None, a2a_algo="bine",
+                                        sdtype=None, rdtype=None, shard_counts=None, send_ws=None, recv_ws=None):
+    """mx_reduce_scatter_multi_ef on every virtual rank: sbufs, res and rbufs
+    one list of tensors per rank, the rest as loopback_mx_reduce_scatter_multi.
+    Returns (status, per-rank statuses)."""
+    P = len(comms)
+    n = len(rbufs[0])
+    if any(len(x) != P for x in (sbufs, res, rbufs)) or any(len(r) != n for x in (sbufs, res, rbufs) for r in x):
+        raise ValueError("loopback_mx_reduce_scatter_multi_ef: the ranks' lists differ in length")
+    s = _mx_rs_scale(op, scale, comms[0])
+    if shard_counts is None:
+        shard_counts = [t.numel() for t in rbufs[0]]
+    need = P * mx_wire_bytes(list(shard_counts), fmt)[1]
+    flat = lambda x: [t for r in x for t in r]  # noqa: E731
+    if send_ws is None or recv_ws is None:
+        import torch
+        dev = _dev_of(flat(rbufs) + flat(sbufs))
+        mk = lambda: [torch.empty(max(need, 16), dtype=torch.uint8, device=dev) for _ in range(P)]  # noqa: E731
+        send_ws = mk() if send_ws is None else send_ws
+        recv_ws = mk() if recv_ws is None else recv_ws
+    ws = [w.numel() for w in list(send_ws) + list(recv_ws) if hasattr(w, "numel")]
+    ws_bytes = min(ws) if ws else need
+    st = (ctypes.c_int * P)()
+    hs = (ctypes.c_void_p * P)(*[c.handle.value for c in comms])
+    rc = lib().bine_loopback_run_mx_reduce_scatter_multi_ef(
+        hs, P, _algo("alltoall", a2a_algo), n, _ptrs(flat(sbufs)), _ptrs(flat(res)), _ptrs(flat(rbufs)),
+        (ctypes.c_size_t * max(n, 1))(*shard_counts), _adamw_dtype(sdtype, flat(sbufs)),
+        _adamw_dtype(rdtype, flat(rbufs)), _mx(fmt), s, _ptrs(send_ws), _ptrs(recv_ws), ws_bytes, st)
+    return rc, list(st)
+
+
 def allreduce_staged(algo, host_sbuf, host_rbuf, dev_sbuf, dev_rbuf, count: int, dtype, op: str, comm: Comm,
                      h2d_stream, d2h_stream, segsize: int = 0, chunk_bytes: int = 0, stream=None) -> None:
     """bine_allreduce_staged: host buffers (page-locked) staged through the
@@ -1805,6 +1901,7 @@ __all__ = ["Comm", "BineError", "IN_PLACE", "schedule", "dm_fused_plan", "dm_fus
            "mx_dbytes", "mx_scale_host", "plan_mx", "mx_quant_segments", "mx_dequant_segments", "mx_quant_multi",
            "loopback_mx_quant_multi", "mx_wire_bytes", "plan_mx_sum", "mx_sum_segments", "mx_reduce_scatter_multi",
            "loopback_mx_reduce_scatter_multi",
+           "mx_quant_ef_segments", "plan_mx_ef", "mx_reduce_scatter_multi_ef", "loopback_mx_reduce_scatter_multi_ef",
            "set_reduce_tuning", "allreduce", "reduce_scatter", "reduce", "loopback_allreduce",
            "loopback_reduce_scatter", "loopback_reduce", "plan", "allgather", "loopback_allgather", "bcast", "loopback_bcast", "reduce_batch",
            "gather", "scatter", "alltoall", "loopback_gather", "loopback_scatter", "loopback_alltoall",

@@ -577,6 +577,35 @@ int mx_rs_args(int P, int n, const void *const *sbufs, void *const *rbufs, const
 int launch_mx_sum_segments_h16(const std::vector<MxLaunch> &ls, const std::vector<uint64_t> &off, int n, int nstreams,
                                const void *packed, size_t block_bytes, void *const *dst, const size_t *counts,
                                int ddtype, int fmt, float scale, void *stream);
+// k_mx_ef_segs (bine_mx_quant_ef_segments): plan_mx_launches' table over the
+// source -- the same tiles -- cut at kMxEfSegsPerLaunch descriptors (four
+// pointers and a count: 112 would not fit the 4 KiB of by-value arguments).
+// The vector body needs what mx_body asks of the source and data8, and res on
+// a 16-B boundary.
+constexpr int kMxEfSegsPerLaunch = BINE_MX_EF_SEGS_PER_LAUNCH;
+struct MxEfLaunch : LaunchTable<kMxEfSegsPerLaunch> {
+  uint64_t elem[(kMxEfSegsPerLaunch + 63) / 64] = {};  // bit s: slot s takes the element body
+};
+inline int mx_ef_body(uint64_t src, uint64_t res, uint64_t data8, size_t esz, int fmt) {
+  return mx_body(src, data8, esz, fmt) || res % 16 ? 1 : 0;
+}
+// The checks of the four lists that need no device, in the header's order
+// (dtype and fmt through the residual's alignment), then the launches.
+int plan_mx_ef_launches(int n, const uint64_t *src, const uint64_t *res, const uint64_t *data8, const uint64_t *scl8,
+                        const size_t *counts, int dtype, int fmt, std::vector<MxEfLaunch> &out);
+// Every check of bine_mx_quant_ef_segments, nothing launched; ls: the launches, where given.
+int mx_ef_args(int n, const void *const *src, const void *const *res, const void *const *data8,
+               const void *const *scl8, const size_t *counts, int dtype, int fmt, const char **why,
+               std::vector<MxEfLaunch> *ls);
+// bine_mx_reduce_scatter_multi_ef's checks that need no communicator and no
+// algorithm id: mx_rs_args' in its order, with res beside sbufs
+int mx_ef_rs_args(int P, int n, const void *const *sbufs, const void *const *res, void *const *rbufs,
+                  const size_t *shard_counts, int sdtype, int rdtype, int fmt, const void *send_ws,
+                  const void *recv_ws, size_t ws_bytes, const char **why, uint64_t *block,
+                  std::vector<uint64_t> *off);
+int launch_mx_quant_ef_segments_h16(const std::vector<MxEfLaunch> &ls, const void *const *src, void *const *res,
+                                    void *const *dst8, void *const *scl8, const size_t *counts, int sdtype, int fmt,
+                                    void *stream);
 int launch_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream);
 
 // direct peer-memory transport (direct.cpp): one launch moves up to kMaxDm

@@ -2141,6 +2141,15 @@ int bine_mx_sum_segments(int n, int nstreams, const void *packed, size_t block_b
                                     stream);
 }
 
+int bine_mx_quant_ef_segments(int n, const void *const *src, void *const *res, void *const *dst8,
+                              void *const *scl8, const size_t *counts, int sdtype, int fmt, void *stream) {
+  const char *why = nullptr;
+  std::vector<MxEfLaunch> ls;
+  if (const int rc = mx_ef_args(n, src, res, dst8, scl8, counts, sdtype, fmt, &why, &ls))
+    return fp8_refused(__func__, rc, why);
+  return launch_mx_quant_ef_segments_h16(ls, src, res, dst8, scl8, counts, sdtype, fmt, stream);
+}
+
 int bine_fill_pico(void *buf, size_t count, int dtype, uint32_t seed, void *stream) {
   return launch_fill_pico(buf, count, dtype, seed, stream);
 }
@@ -2993,6 +3002,66 @@ int bine_mx_reduce_scatter_multi(bine_comm_t c, int a2a_algo, int n, const void 
   return bine_mx_sum_segments(n, c->size, recv_ws, (size_t)B, rbufs, shard_counts, rdtype, fmt, scale, stream);
 }
 
+// the checks of the error-feedback form that need no communicator, for P ranks
+static int mx_ef_rs_multi_args(int P, int a2a_algo, int n, const void *const *sbufs, const void *const *res,
+                               void *const *rbufs, const size_t *shard_counts, int sdtype, int rdtype, int fmt,
+                               const void *send_ws, const void *recv_ws, size_t ws_bytes, const char **why,
+                               uint64_t *block = nullptr, std::vector<uint64_t> *off = nullptr) {
+  if (const int rc = mx_ef_rs_args(P, n, sbufs, res, rbufs, shard_counts, sdtype, rdtype, fmt, send_ws, recv_ws,
+                                   ws_bytes, why, block, off))
+    return rc;
+  if (a2a_algo != BINE_A2A_BINE) {
+    *why = "a2a_algo: BINE_A2A_BINE";
+    return BINE_ERR_UNSUPPORTED;
+  }
+  return BINE_SUCCESS;
+}
+
+int bine_mx_reduce_scatter_multi_ef(bine_comm_t c, int a2a_algo, int n, const void *const *sbufs, void *const *res,
+                                    void *const *rbufs, const size_t *shard_counts, int sdtype, int rdtype, int fmt,
+                                    double scale, void *send_ws, void *recv_ws, size_t ws_bytes, void *stream) {
+  const char *why = nullptr;
+  uint64_t B = 0;
+  std::vector<uint64_t> off;  // per tensor the data offset in a block, then the scale offset
+  if (const int rc = mx_ef_rs_multi_args(c ? c->size : 1, a2a_algo, n, sbufs, res, rbufs, shard_counts, sdtype, rdtype,
+                                         fmt, send_ws, recv_ws, ws_bytes, &why, &B, &off))
+    return fp8_refused(__func__, rc, why);
+  if (!c) return fp8_refused(__func__, BINE_ERR_ARG, "comm NULL");
+  if (c->size > kMxSumMaxStreams)
+    return fp8_refused(__func__, BINE_ERR_UNSUPPORTED, "more ranks than bine_mx_sum_segments takes streams");
+  if (B == 0) return BINE_SUCCESS;
+  const size_t P = (size_t)c->size, ssz = adamw_esz(sdtype);
+  // 1. the n * P (tensor, destination) pairs, destination major, as one list of
+  // bine_mx_quant_ef_segments' -- in runs of at most BINE_MULTI_MAX entries
+  std::vector<const void *> src;
+  std::vector<void *> rs, d8, s8;
+  std::vector<size_t> cnt;
+  for (size_t j = 0; j < P; j++)
+    for (int k = 0; k < n; k++) {
+      if (!shard_counts[k]) continue;
+      char *blk = (char *)send_ws + j * B;
+      src.push_back((const char *)sbufs[k] + j * shard_counts[k] * ssz);
+      rs.push_back((char *)res[k] + j * shard_counts[k] * sizeof(float));
+      d8.push_back(blk + off[(size_t)k]);
+      s8.push_back(blk + off[(size_t)n + k]);
+      cnt.push_back(shard_counts[k]);
+    }
+  std::vector<MxEfLaunch> ls;
+  for (size_t i = 0; i < src.size(); i += BINE_MULTI_MAX) {
+    const int m = (int)std::min<size_t>(BINE_MULTI_MAX, src.size() - i);
+    if (const int rc = mx_ef_args(m, src.data() + i, rs.data() + i, d8.data() + i, s8.data() + i, cnt.data() + i,
+                                  sdtype, fmt, &why, &ls))
+      return fp8_refused(__func__, rc, why);
+    if (const int rc = launch_mx_quant_ef_segments_h16(ls, src.data() + i, rs.data() + i, d8.data() + i,
+                                                       s8.data() + i, cnt.data() + i, sdtype, fmt, stream))
+      return rc;
+  }
+  // 2. block j to rank j
+  if (const int rc = bine_alltoall(c, a2a_algo, send_ws, recv_ws, (size_t)B, BINE_UINT8, stream)) return rc;
+  // 3. rank 0's contribution first, then 1, 2, ...
+  return bine_mx_sum_segments(n, c->size, recv_ws, (size_t)B, rbufs, shard_counts, rdtype, fmt, scale, stream);
+}
+
 // host staging: `per` = flat pipeline chunk per block piece, from the bytes one
 // exchange round carries over all blocks
 // host_sbuf / host_rbuf NULL: that buffer is already on the device (dev_sbuf /
@@ -3407,6 +3476,30 @@ int bine_loopback_run_mx_reduce_scatter_multi(bine_comm_t *comms, int nranks, in
     (void)hipSetDevice(comms[r]->device);
     return bine_mx_reduce_scatter_multi(comms[r], a2a_algo, n, at(sbufs, r), at(rbufs, r), shard_counts, sdtype,
                                         rdtype, fmt, scale, send_ws[r], recv_ws[r], ws_bytes, comms[r]->stream);
+  });
+}
+
+int bine_loopback_run_mx_reduce_scatter_multi_ef(bine_comm_t *comms, int nranks, int a2a_algo, int n,
+                                                 const void *const *sbufs, void *const *res, void *const *rbufs,
+                                                 const size_t *shard_counts, int sdtype, int rdtype, int fmt,
+                                                 double scale, void *const *send_ws, void *const *recv_ws,
+                                                 size_t ws_bytes, int *statuses) {
+  auto at = [&](auto *list, int r) { return list && n > 0 ? list + (size_t)r * n : list; };
+  // before any thread, stream or HIP call: what a rank would refuse without a communicator
+  const char *why = "send_ws or recv_ws NULL";
+  int bad = send_ws && recv_ws ? BINE_SUCCESS : BINE_ERR_ARG;
+  for (int r = 0; !bad && r < nranks; r++)
+    bad = mx_ef_rs_multi_args(nranks, a2a_algo, n, at(sbufs, r), at(res, r), at(rbufs, r), shard_counts, sdtype,
+                              rdtype, fmt, send_ws[r], recv_ws[r], ws_bytes, &why);
+  if (bad) {
+    for (int r = 0; statuses && r < nranks; r++) statuses[r] = bad;
+    return fp8_refused(__func__, bad, why);
+  }
+  return run_threads(comms, nranks, statuses, [&](int r) {
+    (void)hipSetDevice(comms[r]->device);
+    return bine_mx_reduce_scatter_multi_ef(comms[r], a2a_algo, n, at(sbufs, r), at(res, r), at(rbufs, r),
+                                           shard_counts, sdtype, rdtype, fmt, scale, send_ws[r], recv_ws[r],
+                                           ws_bytes, comms[r]->stream);
   });
 }
 

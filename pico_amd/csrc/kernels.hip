@@ -3129,6 +3129,217 @@ int launch_mx_sum_segments_h16(const std::vector<MxLaunch> &ls, const std::vecto
     return BINE_SUCCESS;
   });
 }
+
+// ----------------------------------------------------------------------------
+// MX quantization with an error-feedback residual (bine_mx_quant_ef_segments,
+// bine_amd.h): k_mx_ef_segs.  k_mx_segs' quantizing form over the same tile
+// table of the source, with v = widen(x) + r in x's place and r = v - decode *
+// 2^(S - 127) stored back: one pass, no LDS, no atomics, no barrier.  A block
+// lives in 8 (float) or 4 (16-bit) adjacent lanes of the vector body, in 32 of
+// the element body.  The codes come from mx_quant16<float> / mx_quant1<float>
+// on v, so they are k_mx_segs' bytes for a float source v by construction.
+
+// The value of a code the quantizer wrote, exactly.  FP8: the conversion
+// instruction, which has no branch between the normal and the subnormal codes
+// (fp8_decode_bits has one, two with dequant1's NaN test: DESIGN.md 6.11); the
+// quantizer clamps, so no NaN or infinity code reaches it.  B: the byte of w.
+template <int FMT, int B>
+__device__ __forceinline__ float mx_ef_value(uint32_t w) {
+  if constexpr (FMT == BINE_MX_E4M3) return __builtin_amdgcn_cvt_f32_fp8((int)w, B);
+  else if constexpr (FMT == BINE_MX_E5M2) return __builtin_amdgcn_cvt_f32_bf8((int)w, B);
+  else {
+    const uint32_t d = fp4_decode_bits((w >> (4 * B)) & 15u);
+    float f;
+    __builtin_memcpy(&f, &d, 4);
+    return f;
+  }
+}
+// Four values v of one block under its scale byte S: their codes (four bytes,
+// or four nibbles in the low half), and r = v - decode * 2^(S - 127) -- one
+// multiplication, exact, and one subtraction; +0.0 under S = 0xFF.
+template <int FMT>
+__device__ __forceinline__ uint32_t mx_ef_quad(f32x4 v, uint32_t S, f32x4 &r) {
+  u32x4 vb;
+  __builtin_memcpy(&vb, &v, 16);
+  const uint32_t w = (uint32_t)mx_quant16<float, FMT>(vb, S);
+  const float f = mx_dfactor(S);
+  const f32x4 d = {mx_ef_value<FMT, 0>(w) * f, mx_ef_value<FMT, 1>(w) * f, mx_ef_value<FMT, 2>(w) * f,
+                   mx_ef_value<FMT, 3>(w) * f};
+  const f32x4 e = v - d;
+  r = S == 0xffu ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : e;
+  return w;
+}
+__device__ __forceinline__ uint32_t mx_ef_mag(f32x4 v) {
+  u32x4 b;
+  __builtin_memcpy(&b, &v, 16);
+  return mag16<float>(b);
+}
+
+// One descriptor per slot: the source, the residual, the data bytes, the scale
+// bytes, the element count.
+struct MxEfSeg {
+  uint8_t *src, *res, *d8, *sc;
+  uint64_t n;  // elements
+};
+template <int N>
+struct MxEfSegsOf {
+  TileTable<N> tab;
+  uint64_t elem[(N + 63) / 64];  // bit s: slot s takes the element body
+  MxEfSeg s[N];
+};
+using MxEfSegs = MxEfSegsOf<kMxEfSegsPerLaunch>;
+static_assert(sizeof(MxEfSegs) <= 4096, "by-value kernel arguments: within HIP's 4 KiB");
+static_assert(sizeof(MxEfSegsOf<kMxEfSegsPerLaunch + 1>) > 4096, "BINE_MX_EF_SEGS_PER_LAUNCH is the largest that fits");
+
+template <typename T, int FMT>
+__global__ __launch_bounds__(kBlock) void k_mx_ef_segs(MxEfSegs a) {
+  constexpr size_t V = 16 / sizeof(T);         // elements of one source vector
+  constexpr int RV = (int)(V / 4);             // residual vectors per source vector
+  constexpr int LOG = sizeof(T) == 4 ? 3 : 2;  // log2 of the lanes that hold one block (32 / V)
+  constexpr size_t TV = (size_t)kBlock * kScaleU;
+  using DW = mxw_of<T, FMT>;
+  const auto [k, wt] = a.tab.find(blockIdx.x);
+  const T *src = reinterpret_cast<const T *>(a.s[k].src);
+  float *res = reinterpret_cast<float *>(a.s[k].res);
+  uint8_t *d8 = a.s[k].d8, *sc = a.s[k].sc;
+  const size_t n = a.s[k].n;
+  const bool elem = (a.elem[k >> 6] >> (k & 63)) & 1;
+  // the tile's elements [lo, hi); the vector body takes its whole blocks [lo, vend)
+  const size_t lo = (size_t)wt * TV * V;
+  const size_t hi = lo + TV * V < n ? lo + TV * V : n;
+  const size_t vend = elem ? lo : hi & ~(size_t)(kMxBlock - 1);
+  // one source vector x and its residual vectors r: the data word, the new residuals, the scale byte
+  auto one = [&](u32x4 x, f32x4 (&r)[RV], uint32_t &S) -> DW {
+    f32x4 v[RV];
+    if constexpr (sizeof(T) == 4) {
+      __builtin_memcpy(&v[0], &x, 16);
+      v[0] = v[0] + r[0];
+    } else {
+      const W8 w = widen16<T>(x);
+      v[0] = w.a + r[0];
+      v[1] = w.b + r[1];
+    }
+    uint32_t m = mx_ef_mag(v[0]);
+    if constexpr (RV == 2) {
+      const uint32_t m1 = mx_ef_mag(v[1]);
+      m = m1 > m ? m1 : m;
+    }
+    S = mx_scale_rule(mx_group_max<LOG>(m), FMT);
+    uint32_t w[RV];
+#pragma unroll
+    for (int j = 0; j < RV; j++) w[j] = mx_ef_quad<FMT>(v[j], S, r[j]);
+    DW d;
+    if constexpr (RV == 1) {
+      d = (DW)w[0];
+    } else if constexpr (FMT == BINE_MX_E2M1) {
+      d = w[0] | (w[1] << 16);
+    } else {
+      d = DW{w[0], w[1]};
+    }
+    return d;
+  };
+  if (vend > lo) {
+    const size_t nv = (vend - lo) / V;  // a multiple of the lanes of a block
+    const u32x4 *vx = reinterpret_cast<const u32x4 *>(src) + lo / V;
+    f32x4 *vr = reinterpret_cast<f32x4 *>(res) + lo / 4;
+    DW *vd = reinterpret_cast<DW *>(d8) + lo / V;
+    uint8_t *vs = sc + lo / kMxBlock;
+    const size_t t = threadIdx.x;
+    if (nv == TV) {  // a full tile: every load issued before the first use
+      u32x4 x[kScaleU];
+      f32x4 r[kScaleU][RV];
+#pragma unroll
+      for (int u = 0; u < kScaleU; u++) {
+        const size_t i = t + (size_t)u * kBlock;
+        x[u] = __builtin_nontemporal_load(vx + i);
+#pragma unroll
+        for (int j = 0; j < RV; j++) r[u][j] = __builtin_nontemporal_load(vr + i * RV + j);
+      }
+#pragma unroll
+      for (int u = 0; u < kScaleU; u++) {
+        const size_t i = t + (size_t)u * kBlock;
+        uint32_t S;
+        const DW d = one(x[u], r[u], S);
+        __builtin_nontemporal_store(d, vd + i);
+#pragma unroll
+        for (int j = 0; j < RV; j++) __builtin_nontemporal_store(r[u][j], vr + i * RV + j);
+        if ((t & ((1u << LOG) - 1)) == 0) __builtin_nontemporal_store((uint8_t)S, vs + (i >> LOG));
+      }
+    } else {
+#pragma unroll 1
+      for (int u = 0; u < kScaleU; u++) {
+        const size_t i = t + (size_t)u * kBlock;
+        const bool in = i < nv;  // the same in all lanes of a block
+        // every lane takes part in the cross-lane maximum: the loads and the stores are guarded, not it
+        u32x4 x = {0, 0, 0, 0};
+        f32x4 r[RV] = {};
+        if (in) {
+          x = vx[i];
+#pragma unroll
+          for (int j = 0; j < RV; j++) r[j] = vr[i * RV + j];
+        }
+        uint32_t S;
+        const DW d = one(x, r, S);
+        if (in) {
+          __builtin_nontemporal_store(d, vd + i);
+#pragma unroll
+          for (int j = 0; j < RV; j++) __builtin_nontemporal_store(r[j], vr + i * RV + j);
+          if ((t & ((1u << LOG) - 1)) == 0) __builtin_nontemporal_store((uint8_t)S, vs + (i >> LOG));
+        }
+      }
+    }
+  }
+  // the element body: [vend, hi), one element per lane, 32 adjacent lanes a
+  // block (vend is a block's first element and kBlock a multiple of 32); the
+  // lanes of a block leave the loop together
+#pragma unroll 1
+  for (size_t i = vend + threadIdx.x; (i & ~(size_t)(kMxBlock - 1)) < hi; i += kBlock) {
+    const bool in = i < hi;
+    float x = 0.0f, r = 0.0f;  // a lane past the end: v = +0, code 0
+    if (in) {
+      x = adamw_widen<T>(src[i]);
+      r = res[i];
+    }
+    const float v = x + r;
+    uint32_t vb;
+    __builtin_memcpy(&vb, &v, 4);
+    const uint32_t S = mx_scale_rule(mx_group_max<5>(vb & 0x7fffffffu), FMT);
+    const uint32_t q = S == 0xffu ? 0u : mx_quant1<float, FMT>(v, S);
+    const float e = v - mx_ef_value<FMT, 0>(q) * mx_dfactor(S);
+    if constexpr (FMT == BINE_MX_E2M1) {
+      const uint32_t other = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q, 0xB1, 0xf, 0xf, false);  // lane ^ 1
+      if (in && !(i & 1)) __builtin_nontemporal_store((uint8_t)(q | (other << 4)), d8 + (i >> 1));
+    } else {
+      if (in) __builtin_nontemporal_store((uint8_t)q, d8 + i);
+    }
+    if (in) __builtin_nontemporal_store(S == 0xffu ? 0.0f : e, res + i);
+    if ((i & (kMxBlock - 1)) == 0) __builtin_nontemporal_store((uint8_t)S, sc + i / kMxBlock);
+  }
+}
+
+int launch_mx_quant_ef_segments_h16(const std::vector<MxEfLaunch> &ls, const void *const *src, void *const *res,
+                                    void *const *dst8, void *const *scl8, const size_t *counts, int sdtype, int fmt,
+                                    void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  return with_adamw_dtype(sdtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    for (const MxEfLaunch &L : ls) {
+      MxEfSegs a;
+      for (size_t w = 0; w < sizeof a.elem / sizeof a.elem[0]; w++) a.elem[w] = L.elem[w];
+      fill_segs(a, L, [&](int s) {
+        const int k = L.seg[s];
+        return MxEfSeg{(uint8_t *)const_cast<void *>(src[k]), (uint8_t *)res[k], (uint8_t *)dst8[k],
+                       (uint8_t *)scl8[k], (uint64_t)counts[k]};
+      });
+      const dim3 grid(L.tile0[L.nseg]), blk(kBlock);
+      if (fmt == BINE_MX_E4M3) hipLaunchKernelGGL((k_mx_ef_segs<T, BINE_MX_E4M3>), grid, blk, 0, st, a);
+      else if (fmt == BINE_MX_E5M2) hipLaunchKernelGGL((k_mx_ef_segs<T, BINE_MX_E5M2>), grid, blk, 0, st, a);
+      else hipLaunchKernelGGL((k_mx_ef_segs<T, BINE_MX_E2M1>), grid, blk, 0, st, a);
+      if (hipGetLastError() != hipSuccess) return BINE_ERR_HIP;
+    }
+    return BINE_SUCCESS;
+  });
+}
 #endif  // BINE_OPSET == 2
 
 #if BINE_OPSET == 0

@@ -29,6 +29,10 @@
 //                                            (mx_wire_layout, bine_mx_wire_bytes) and the refusals of the
 //                                            sum and of the MX reduce-scatter (mx_sum_args, mx_rs_args;
 //                                            tools/mxrs_check.cpp)
+//   plan_mx_ef_launches / bine_plan_mx_ef    k_mx_ef_segs: plan_mx_launches' tiles over the source, cut at
+//                                            kMxEfSegsPerLaunch descriptors, the body flag of source, data
+//                                            and residual; the refusals of the error-feedback calls
+//                                            (mx_ef_args, mx_ef_rs_args; tools/mxef_check.cpp)
 // Dynamic loss scaling keeps its host half here too:
 // bine_step_state_init, the refusals (step_update_args, adamw_dyn_args) and
 // bine_step_update_host, the host compilation of the statement k_step_update
@@ -326,6 +330,28 @@ int quant_args(int n, const void *const *wide, const void *const *bytes8, const 
   return BINE_SUCCESS;
 }
 
+// The MX tile rule, called by plan_mx_launches (k_mx_segs, and through it
+// plan_mx_sum_launches for k_mx_sum_segs) and by plan_mx_ef_launches: tiles
+// of kCopyTileVecs * 16 bytes of esz-byte elements counted from the segment's
+// first element, at least one per non-empty segment, at most N slots per
+// launch; elem(k) = 1 where tensor k takes the element body.
+template <int N, typename L, typename F>
+static int mx_tiles(int n, const size_t *counts, size_t esz, std::vector<L> &out, F &&elem) {
+  const uint64_t tile_elems = kCopyTileVecs * 16 / esz;  // whole blocks: a multiple of kMxBlock
+  for (int k = 0; k < n; k++) {
+    if (counts[k] == 0) continue;
+    const uint64_t tiles = (counts[k] + tile_elems - 1) / tile_elems;
+    if (tiles > kSegMaxWgs) return BINE_ERR_ARG;
+    if (out.empty() || out.back().nseg == N || out.back().tile0[out.back().nseg] + tiles > kSegMaxWgs)
+      out.emplace_back();
+    L &l = out.back();
+    const int s = l.nseg++;
+    l.seg[s] = k;
+    l.tile0[s + 1] = (uint32_t)(l.tile0[s] + tiles);
+    if (elem(k)) l.elem[s >> 6] |= (uint64_t)1 << (s & 63);
+  }
+  return BINE_SUCCESS;
+}
 
 int plan_mx_launches(int n, const uint64_t *wide, const uint64_t *data8, const uint64_t *scl8, const size_t *counts,
                      int dtype, int fmt, std::vector<MxLaunch> &out) {
@@ -340,19 +366,41 @@ int plan_mx_launches(int n, const uint64_t *wide, const uint64_t *data8, const u
     if (counts[k] && wide[k] % esz) return BINE_ERR_ARG;
     if (counts[k] > ((size_t)1 << 56)) return BINE_ERR_ARG;  // keeps the byte count and every sum below 2^64
   }
-  const uint64_t tile_elems = kCopyTileVecs * 16 / esz;  // whole blocks: a multiple of kMxBlock
+  return mx_tiles<kMxSegsPerLaunch>(n, counts, esz, out, [&](int k) { return mx_body(wide[k], data8[k], esz, fmt); });
+}
+
+int plan_mx_ef_launches(int n, const uint64_t *src, const uint64_t *res, const uint64_t *data8, const uint64_t *scl8,
+                        const size_t *counts, int dtype, int fmt, std::vector<MxEfLaunch> &out) {
+  out.clear();
+  const size_t esz = adamw_esz(dtype);
+  if (!esz || !mx_fmt_ok(fmt)) return BINE_ERR_ARG;
+  if (n < 0 || n > BINE_MULTI_MAX) return BINE_ERR_ARG;
+  if (n > 0 && (!src || !res || !data8 || !scl8 || !counts)) return BINE_ERR_ARG;
+  for (int k = 0; k < n; k++)
+    if (counts[k] && (!src[k] || !res[k] || !data8[k] || !scl8[k])) return BINE_ERR_ARG;
   for (int k = 0; k < n; k++) {
-    if (counts[k] == 0) continue;
-    const uint64_t tiles = (counts[k] + tile_elems - 1) / tile_elems;
-    if (tiles > kSegMaxWgs) return BINE_ERR_ARG;
-    if (out.empty() || out.back().nseg == kMxSegsPerLaunch || out.back().tile0[out.back().nseg] + tiles > kSegMaxWgs)
-      out.emplace_back();
-    MxLaunch &L = out.back();
-    const int s = L.nseg++;
-    L.seg[s] = k;
-    L.tile0[s + 1] = (uint32_t)(L.tile0[s] + tiles);
-    if (mx_body(wide[k], data8[k], esz, fmt)) L.elem[s >> 6] |= (uint64_t)1 << (s & 63);
+    if (counts[k] && src[k] % esz) return BINE_ERR_ARG;
+    if (counts[k] > ((size_t)1 << 56)) return BINE_ERR_ARG;  // keeps the byte count and every sum below 2^64
   }
+  for (int k = 0; k < n; k++)
+    if (counts[k] && res[k] % 4) return BINE_ERR_ARG;
+  return mx_tiles<kMxEfSegsPerLaunch>(n, counts, esz, out,
+                                      [&](int k) { return mx_ef_body(src[k], res[k], data8[k], esz, fmt); });
+}
+
+int mx_ef_args(int n, const void *const *src, const void *const *res, const void *const *data8,
+               const void *const *scl8, const size_t *counts, int dtype, int fmt, const char **why,
+               std::vector<MxEfLaunch> *ls) {
+  if (!adamw_esz(dtype)) return refuse(why, "sdtype: float, float16 or bfloat16");
+  if (!mx_fmt_ok(fmt)) return refuse(why, "fmt: BINE_MX_E4M3, BINE_MX_E5M2 or BINE_MX_E2M1");
+  std::vector<uint64_t> a;  // src, res, data8, scl8
+  if (seg_list_addrs(n, counts, {src, res, data8, scl8}, a))
+    return refuse(why, "n outside [0, BINE_MULTI_MAX], or a NULL array");
+  std::vector<MxEfLaunch> local;
+  const uint64_t *p = a.data();
+  if (plan_mx_ef_launches(n, p, p + n, p + 2 * (size_t)n, p + 3 * (size_t)n, counts, dtype, fmt, ls ? *ls : local))
+    return refuse(why, "a NULL buffer with a non-zero count, a source not aligned to its element, or a residual not "
+                       "4-byte aligned");
   return BINE_SUCCESS;
 }
 
@@ -452,21 +500,26 @@ int mx_sum_args(int n, int nstreams, const void *packed, size_t block_bytes, voi
   return BINE_SUCCESS;
 }
 
-int mx_rs_args(int P, int n, const void *const *sbufs, void *const *rbufs, const size_t *shard_counts, int sdtype,
-               int rdtype, int fmt, const void *send_ws, const void *recv_ws, size_t ws_bytes, const char **why,
-               uint64_t *block, std::vector<uint64_t> *off) {
+// ef: res is a third list beside sbufs (binary32, 4-byte aligned); otherwise it is not looked at
+static int mx_rs_args_of(bool ef, int P, int n, const void *const *sbufs, const void *const *res, void *const *rbufs,
+                         const size_t *shard_counts, int sdtype, int rdtype, int fmt, const void *send_ws,
+                         const void *recv_ws, size_t ws_bytes, const char **why, uint64_t *block,
+                         std::vector<uint64_t> *off) {
   if (block) *block = 0;
   const size_t ssz = adamw_esz(sdtype), rsz = adamw_esz(rdtype);
   if (!ssz || !rsz) return refuse(why, "sdtype, rdtype: float, float16 or bfloat16");
   if (!mx_fmt_ok(fmt)) return refuse(why, "fmt: BINE_MX_E4M3, BINE_MX_E5M2 or BINE_MX_E2M1");
-  std::vector<uint64_t> a;  // sbufs, rbufs
-  if (seg_list_addrs(n, shard_counts, {sbufs, rbufs}, a))
+  std::vector<uint64_t> a, ar;  // sbufs, rbufs; res where ef
+  if (seg_list_addrs(n, shard_counts, {sbufs, rbufs}, a) || (ef && seg_list_addrs(n, shard_counts, {res}, ar)))
     return refuse(why, "n outside [0, BINE_MULTI_MAX], or a NULL array");
   for (int k = 0; k < n; k++)
-    if (shard_counts[k] && (!a[k] || !a[(size_t)n + k])) return refuse(why, "a NULL buffer with a non-zero count");
+    if (shard_counts[k] && (!a[k] || !a[(size_t)n + k] || (ef && !ar[k])))
+      return refuse(why, "a NULL buffer with a non-zero count");
   for (int k = 0; k < n; k++)
     if (shard_counts[k] && (a[k] % ssz || a[(size_t)n + k] % rsz))
       return refuse(why, "a source or destination not aligned to its element");
+  for (int k = 0; k < n; k++)
+    if (ef && shard_counts[k] && ar[k] % 4) return refuse(why, "a residual not 4-byte aligned");
   for (int k = 0; k < n; k++)
     if (shard_counts[k] % kMxBlock || shard_counts[k] > (size_t)INT_MAX)
       return refuse(why, "a shard count not a multiple of 32, or above INT_MAX");
@@ -480,6 +533,21 @@ int mx_rs_args(int P, int n, const void *const *sbufs, void *const *rbufs, const
   if (s0 < r0 ? r0 - s0 < ws_bytes : s0 - r0 < ws_bytes) return refuse(why, "send_ws and recv_ws overlap");
   if (ws_bytes / (uint64_t)(P > 0 ? P : 1) < B) return refuse(why, "ws_bytes below comm size * block bytes");
   return BINE_SUCCESS;
+}
+
+int mx_rs_args(int P, int n, const void *const *sbufs, void *const *rbufs, const size_t *shard_counts, int sdtype,
+               int rdtype, int fmt, const void *send_ws, const void *recv_ws, size_t ws_bytes, const char **why,
+               uint64_t *block, std::vector<uint64_t> *off) {
+  return mx_rs_args_of(false, P, n, sbufs, nullptr, rbufs, shard_counts, sdtype, rdtype, fmt, send_ws, recv_ws,
+                       ws_bytes, why, block, off);
+}
+
+int mx_ef_rs_args(int P, int n, const void *const *sbufs, const void *const *res, void *const *rbufs,
+                  const size_t *shard_counts, int sdtype, int rdtype, int fmt, const void *send_ws,
+                  const void *recv_ws, size_t ws_bytes, const char **why, uint64_t *block,
+                  std::vector<uint64_t> *off) {
+  return mx_rs_args_of(true, P, n, sbufs, res, rbufs, shard_counts, sdtype, rdtype, fmt, send_ws, recv_ws, ws_bytes,
+                       why, block, off);
 }
 
 }  // namespace bine
@@ -549,6 +617,25 @@ extern "C" int64_t bine_plan_mx(int n, const uint64_t *wide, const uint64_t *dat
   int64_t nt = 0;
   for (size_t l = 0; l < ls.size(); l++) {
     const bine::MxLaunch &L = ls[l];
+    for (int s = 0; s < L.nseg; s++, nt++)
+      if (out && nt < cap) {
+        uint64_t *e = out + 5 * nt;
+        e[0] = l, e[1] = (uint64_t)L.seg[s], e[2] = L.tile0[s], e[3] = L.tile0[s + 1] - L.tile0[s];
+        e[4] = (L.elem[s >> 6] >> (s & 63)) & 1;
+      }
+  }
+  return nt;
+}
+
+extern "C" int64_t bine_plan_mx_ef(int n, const uint64_t *src, const uint64_t *res, const uint64_t *data8,
+                                   const uint64_t *scl8, const size_t *counts, int dtype, int fmt, uint64_t *out,
+                                   int64_t cap) {
+  std::vector<bine::MxEfLaunch> ls;
+  const int rc = bine::plan_mx_ef_launches(n, src, res, data8, scl8, counts, dtype, fmt, ls);
+  if (rc) return -(int64_t)rc;
+  int64_t nt = 0;
+  for (size_t l = 0; l < ls.size(); l++) {
+    const bine::MxEfLaunch &L = ls[l];
     for (int s = 0; s < L.nseg; s++, nt++)
       if (out && nt < cap) {
         uint64_t *e = out + 5 * nt;
